@@ -9,6 +9,12 @@ Weak scaling: global_batch = batch_per_gpu * N (per-GPU work fixed as N grows).
 
   python bench.py --gpus N --steps K --warmup W
   (N>1 is launched by the driver via torch.distributed.run, one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line. --dump-outputs DIR additionally writes what the last timed step
+returned (DIR/<name>.npy; inputs and weights are seeded, so the same
+arguments give the same arrays run to run). --full is reserved for
+measurements beyond the headline figure; there are none today.
 """
 from __future__ import annotations
 
@@ -24,6 +30,27 @@ def stage_max_pos(model: str) -> int:
     from bloombee_amd.models.base import resolve_config
 
     return resolve_config(model).max_position_embeddings
+
+
+DUMP_MAX_BYTES = 64 << 20  # cap on everything --dump-outputs writes
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Write what the last timed step returned to its caller as
+    <out_dir>/<name>.npy (float32; token ids < 2^24 are exact). An output
+    past its share of DUMP_MAX_BYTES is cut to a fixed seeded sample of
+    its flattened elements, so two builds dump the same positions."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, len(arrays)) // 4 - 64  # elements, less header
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.size > budget:
+            idx = np.sort(np.random.default_rng(0).choice(
+                a.size, size=budget, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def run_swarm(args):
@@ -159,6 +186,9 @@ def run_swarm(args):
         torch.cuda.synchronize()
     elapsed = time.monotonic() - t0
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"hidden": out, "next_ids": ids})
+
     session.close()
     manager.shutdown()
     # release the workers, then spin down
@@ -214,6 +244,13 @@ def main():
                     help="pipeline = raw RCCL pipeline stages (flagship); "
                          "swarm = the full decentralized serving stack "
                          "(DHT + sessions + handler) over the same device plane")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one "
+                         "returned as DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline "
+                         "figure (none today: a plain run already does only "
+                         "setup, warmup, the timed steps and the result line)")
     args = ap.parse_args()
 
     if args.mode == "swarm":
@@ -320,6 +357,9 @@ def main():
                 "p50_step_ms": round(p50, 3),
             },
         }
+        if args.dump_outputs:
+            # decode_round hands its caller the next token of every sequence
+            dump_outputs(args.dump_outputs, {"next_ids": ids})
         print(json.dumps(result))
     if dist.is_initialized():
         dist.destroy_process_group()

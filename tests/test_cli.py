@@ -157,3 +157,39 @@ def test_bench_swarm_mode_cpu_contract():
     assert out["unit"] == "tokens/s" and out["value"] > 0
     assert "serving stack" in out["metric"]
     assert out["config"]["parallelism"] == "swarm-pp1"
+
+
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_cpu(tmp_path):
+    """bench.py --dump-outputs writes what the last timed step returned
+    (next token ids) as float32 .npy; --steps sets the timed step count,
+    and the same arguments reproduce the same outputs run to run."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    # --full adds nothing to a run that is already lean: same outputs
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = subprocess.run(
+            [sys.executable, "bench.py", "--model", "llama-tiny", "--gpus",
+             "1", "--steps", "3", "--warmup", "1", "--batch-per-gpu", "2",
+             "--prompt", "16", "--device", "cpu", "--dump-outputs", str(d)]
+            + extra,
+            capture_output=True, text=True, timeout=240, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
+        out = json.loads(line)
+        assert out["steps"] == 3 and out["warmup"] == 1
+        assert out["ms_per_step"] > 0
+        assert out["unit"] == "tokens/s" and out["value"] > 0
+        assert sorted(p.name for p in d.iterdir()) == ["next_ids.npy"]
+        a = np.load(d / "next_ids.npy")
+        assert a.dtype == np.float32 and a.shape == (2,)
+        assert np.all(a == np.round(a)) and np.all(a >= 0)
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
