@@ -3,7 +3,7 @@
 Reports per-kernel time and effective HBM bandwidth / TFLOPs so kernel
 changes can be A/B'd without the end-to-end bench's noise.
 
-    python benchmarks/bench_kernels.py [attn_decode attn_prefill norms ...]
+    python benchmarks/bench_kernels.py [attn_decode attn_mixed attn_prefill ...]
 """
 import math
 import os
@@ -47,6 +47,52 @@ def bench_attn_decode():
             t = timeit(lambda: ops.attn_decode(q, kp, vp, pt, ctx_l, n_split=ns))
             print(f"attn_decode B{B} Hq{Hq}/{Hkv} ctx{ctx} D{D} ns={ns}: "
                   f"{t*1e6:8.1f} us  {bytes_/t/1e12:6.2f} TB/s")
+
+
+def bench_attn_mixed():
+    """Mixed-device decode, device side only: the decode kernel in
+    forced-partial mode + the external-partial merge launch, against plain
+    attn_decode at the same shape and against the old per-row torch
+    composition (BBAMD_MIXED_KERNEL=0). The external partials are
+    pre-computed and already on the device, and the host prefix is one page,
+    so host attention time stays out of the figures."""
+    from bloombee_amd.ops import hip_ops
+    from bloombee_amd.ops import interface as iface
+    B, Hq, Hkv, ctx, D, P, S_host = 32, 32, 8, 2048, 128, 16, 16
+    maxp = (ctx + P - 1) // P
+    npages = B * maxp + 1
+    kp = torch.randn(npages, Hkv, P, D, dtype=torch.bfloat16, device=DEV)
+    vp = torch.randn(kp.shape[0], Hkv, D, P, dtype=torch.bfloat16, device=DEV)
+    pt = torch.arange(B * maxp, dtype=torch.int32, device=DEV).reshape(B, maxp)
+    q = torch.randn(B, Hq, 1, D, dtype=torch.bfloat16, device=DEV) * 0.1
+    ctx_l = torch.full((B,), ctx, dtype=torch.int32, device=DEV)
+    hk = torch.randn(B, Hkv, S_host, D)
+    hv = torch.randn(B, Hkv, S_host, D)
+    scale = 1.0 / math.sqrt(D)
+    ml, acc = ref.attn_host_partial(q[:, :, 0].float().cpu(), hk, hv, scale)
+    ml, acc = ml.to(DEV), acc.to(DEV)
+    tag = f"B{B} Hq{Hq}/{Hkv} ctx{ctx} D{D}"
+    t_dec = timeit(lambda: ops.attn_decode(q, kp, vp, pt, ctx_l))
+    print(f"attn_decode        {tag}: {t_dec*1e6:9.1f} us")
+    t_mix = timeit(lambda: hip_ops.attn_decode_mixed(
+        q, kp, vp, pt, ctx_l, ml, acc, scale, 0, 0, None, S_host))
+    print(f"attn_mixed[kernel] {tag}: {t_mix*1e6:9.1f} us  "
+          f"(device only, {t_mix/t_dec:.2f}x attn_decode)")
+    t_e2e = timeit(lambda: ops.attn_paged_mixed(q, kp, vp, pt, ctx_l, hk, hv),
+                   iters=20, warmup=3)
+    print(f"attn_mixed[kernel] {tag}: {t_e2e*1e6:9.1f} us  "
+          f"(end to end: q D2H + host partial S_host={S_host} + H2D)")
+    old = iface._MIXED_KERNEL
+    iface._MIXED_KERNEL = False
+    try:
+        t_old = timeit(lambda: ops.attn_paged_mixed(q, kp, vp, pt, ctx_l,
+                                                    hk, hv),
+                       iters=5, warmup=1)
+    finally:
+        iface._MIXED_KERNEL = old
+    print(f"attn_mixed[torch composition] {tag}: {t_old*1e6:9.1f} us  "
+          f"({t_old/t_e2e:.1f}x the kernel path end to end, "
+          f"{t_old/t_mix:.1f}x its device time)")
 
 
 def bench_attn_prefill():
@@ -141,6 +187,7 @@ def bench_gemm_norm():
 
 ALL = {
     "attn_decode": bench_attn_decode,
+    "attn_mixed": bench_attn_mixed,
     "attn_prefill": bench_attn_prefill,
     "kv_stream": bench_kv_stream,
     "norms": bench_norms,

@@ -73,8 +73,19 @@ class BloomBlock(torch.nn.Module):
         vp = kv.v_pages(self.layer_index)
         pt = kv.page_table()
         ops.kv_write(k, v, kp, vp, pt, start_pos)
-        out = ops.attn_paged(q, kp, vp, pt, start_pos.long(), self.scale,
-                             alibi_slopes=self.alibi)
+        hp = (kv.host_prefix(self.layer_index)
+              if hasattr(kv, "host_prefix") else None)
+        if hp is not None:
+            # mixed-device session (kv.swap_in_as_prefix): host prefix on the
+            # CPU + device recent segment, exact merge. ALiBi positions are
+            # absolute — the op shifts the device segment by the prefix
+            # length; decode-only (backend gates T == 1)
+            out = ops.attn_paged_mixed(q, kp, vp, pt, start_pos + T,
+                                       hp[0], hp[1], self.scale,
+                                       alibi_slopes=self.alibi)
+        else:
+            out = ops.attn_paged(q, kp, vp, pt, start_pos.long(), self.scale,
+                                 alibi_slopes=self.alibi)
         out = out.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
         return ops.linear(out, self.dense_w, bias=self.dense_b)
 

@@ -72,10 +72,25 @@ class FalconBlock(torch.nn.Module):
         kp = kv.k_pages(self.layer_index)
         vp = kv.v_pages(self.layer_index)
         pt = kv.page_table()
+        # mixed-device sessions (host KV prefix + device recent segment):
+        # pool positions are local, rotary stays absolute (see llama block)
+        off = getattr(kv, "pos_offset", 0)
+        if off and position_ids is None:
+            position_ids = (start_pos.view(B, 1) + off
+                            + torch.arange(T, device=hidden.device)
+                            .view(1, T)).int()
         ops.rope_kv_write_(qkv, Hq, Hkv, cos, sin, position_ids, kp, vp, pt,
                            start_pos)
-        attn = ops.attn_paged_qkv(qkv, Hq, Hkv, kp, vp, pt, start_pos,
-                                  self.scale)
+        hp = (kv.host_prefix(self.layer_index)
+              if hasattr(kv, "host_prefix") else None)
+        if hp is not None:
+            # exact two-segment merge; decode-only (backend gates T == 1)
+            attn = ops.attn_paged_mixed_qkv(qkv, Hq, Hkv, kp, vp, pt,
+                                            start_pos + T, hp[0], hp[1],
+                                            self.scale)
+        else:
+            attn = ops.attn_paged_qkv(qkv, Hq, Hkv, kp, vp, pt, start_pos,
+                                      self.scale)
         a = ops.linear(attn, self.o_w)
         # parallel branches: both read the SAME layernorm output
         m = ops.linear(ops.gelu_tanh(ops.linear(x, self.up_w)), self.down_w)

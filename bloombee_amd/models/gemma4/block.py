@@ -122,8 +122,10 @@ class Gemma4Block(torch.nn.Module):
         eps = cfg.rms_norm_eps
         cos, sin = self._tables(hidden.device)
         if position_ids is None:
-            pos = start_pos.view(B, 1).long() + torch.arange(
-                T, device=hidden.device).view(1, T)
+            # mixed-device sessions: start_pos is local to the device pool,
+            # rotary positions stay absolute (kv.pos_offset, see llama block)
+            pos = (start_pos.view(B, 1).long() + getattr(kv, "pos_offset", 0)
+                   + torch.arange(T, device=hidden.device).view(1, T))
         else:
             pos = position_ids.long()
 
@@ -154,9 +156,22 @@ class Gemma4Block(torch.nn.Module):
                     f"gemma-4 shared-KV layer {self.global_index} requires its "
                     f"donor layer {self.donor} in the same server block range")
 
-        attn = ops.attn_paged(q, kv.k_pages(kv_layer), kv.v_pages(kv_layer),
-                              kv.page_table(), start_pos.long(), scale=1.0,
-                              window=self.window)
+        hp = (kv.host_prefix(kv_layer)
+              if hasattr(kv, "host_prefix") else None)
+        if hp is not None:
+            # mixed-device session: the host prefix of the layer whose pools
+            # this block reads (the donor's for shared-KV tail layers).
+            # Sliding layers see only the host suffix still inside the
+            # window; decode-only (backend gates T == 1)
+            attn = ops.attn_paged_mixed(
+                q, kv.k_pages(kv_layer), kv.v_pages(kv_layer),
+                kv.page_table(), start_pos + T, hp[0], hp[1], scale=1.0,
+                window=self.window)
+        else:
+            attn = ops.attn_paged(q, kv.k_pages(kv_layer),
+                                  kv.v_pages(kv_layer), kv.page_table(),
+                                  start_pos.long(), scale=1.0,
+                                  window=self.window)
         attn = attn.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
         a = ops.linear(attn, self.o_w)
         a = _rms1p(a, self.post_attn_norm_w, eps)

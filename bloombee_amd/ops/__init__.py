@@ -10,6 +10,7 @@ from bloombee_amd.ops.interface import (  # noqa: F401
     attn_decode,
     attn_paged,
     attn_paged_mixed,
+    attn_paged_mixed_qkv,
     attn_paged_qkv,
     attn_prefill,
     fuse_norm_linear_ok,

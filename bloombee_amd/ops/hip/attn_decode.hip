@@ -95,6 +95,79 @@ __global__ void attn_decode_combine_kernel(
                   o);
 }
 
+// Mixed-device merge: folds the n_split device partials of one decode launch
+// (written with force_partial) plus ONE external partial per query head —
+// the host-resident KV prefix, attended on the CPU (ops.attn_paged_mixed).
+// Same grid/block as the combine kernel.
+//
+// External partial contract, NATURAL-log units:
+//   ext_ml  (B, Hq, 2) f32: [max score m, sum_j exp(s_j - m)]
+//   ext_acc (B, Hq, D) f32: sum_j exp(s_j - m) * v_j   (un-normalised)
+// with s_j the scaled (+ absolute-position ALiBi) score. l == 0 means "no
+// external positions" and is skipped, m is then ignored. The device
+// partials' m is in log2 units (sc2 = scale * LOG2E in the decode kernels),
+// so the external m is converted here.
+//
+// dev_shift (Hq,) f32 natural-log units or null: per-head constant added to
+// every device score before the merge. The decode kernels bias ALiBi with
+// LOCAL pool positions (slope * j_local); the true bias of a device position
+// is slope * (j_local + pos_offset). The difference is constant over the
+// device segment — invisible inside it, but not across the merge.
+template <int D>
+__global__ void attn_decode_merge_ext_kernel(
+    const float* __restrict__ part_ml, const float* __restrict__ part_acc,
+    const float* __restrict__ ext_ml, const float* __restrict__ ext_acc,
+    const float* __restrict__ dev_shift, unsigned short* __restrict__ out,
+    int Hkv, int G, int nch, int maxg, int n_split, long out_sb, long out_sh) {
+  constexpr int E = D / 16;
+  const int bh = blockIdx.x;           // (b, kvh, chunk)
+  const int b = bh / (Hkv * nch);
+  const int rem = bh % (Hkv * nch);
+  const int kvh = rem / nch;
+  const int g0 = (rem % nch) * maxg;
+  const int g = threadIdx.x / 16;
+  const int li = threadIdx.x & 15;
+  if (g0 + g >= G || g >= maxg) return;
+  const int h = kvh * G + g0 + g;      // query head
+  const float shift2 = (dev_shift != nullptr) ? dev_shift[h] * LOG2E : 0.f;
+  float m2 = NEG_BIG, l = 0.f, acc[E];
+#pragma unroll
+  for (int j = 0; j < E; ++j) acc[j] = 0.f;
+  for (int s = 0; s < n_split; ++s) {
+    const long pbase = (long)bh * n_split + s;
+    const float mo = part_ml[(pbase * maxg + g) * 2 + 0] + shift2;
+    const float lo = part_ml[(pbase * maxg + g) * 2 + 1];
+    if (lo == 0.f) continue;
+    const float mn = fmaxf(m2, mo);
+    const float c1f = fast_exp2(m2 - mn);
+    const float c2f = fast_exp2(mo - mn);
+    l = l * c1f + lo * c2f;
+#pragma unroll
+    for (int j = 0; j < E; ++j)
+      acc[j] = acc[j] * c1f + part_acc[(pbase * maxg + g) * D + li * E + j] * c2f;
+    m2 = mn;
+  }
+  {
+    const long hb = (long)b * (Hkv * G) + h;
+    const float le = ext_ml[hb * 2 + 1];
+    if (le != 0.f) {
+      const float me = ext_ml[hb * 2 + 0] * LOG2E;
+      const float mn = fmaxf(m2, me);
+      const float c1f = fast_exp2(m2 - mn);
+      const float c2f = fast_exp2(me - mn);
+      l = l * c1f + le * c2f;
+#pragma unroll
+      for (int j = 0; j < E; ++j)
+        acc[j] = acc[j] * c1f + ext_acc[hb * D + li * E + j] * c2f;
+    }
+  }
+  float o[E];
+  const float inv = (l > 0.f) ? 1.f / l : 0.f;
+#pragma unroll
+  for (int j = 0; j < E; ++j) o[j] = acc[j] * inv;
+  store_bf16_e<E>(out + (long)b * out_sb + (long)h * out_sh + li * E, o);
+}
+
 // Pure-streaming probe: same grid/walk/loads as attn_decode_kernel but no
 // softmax/acc — measures the access pattern's bandwidth ceiling. NT variant
 // uses nontemporal loads (KV is read-once-per-step; keep L2 for weights).

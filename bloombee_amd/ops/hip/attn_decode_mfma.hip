@@ -57,6 +57,9 @@ DEVINL float quad16_reduce_sum(float x) {
 // shuffle + LDS-relayout overhead per position. Costs ~40 VGPRs (V
 // fragments + score regs for the second tile); host falls back to NT=1 for
 // short splits.
+// force_partial (grid-uniform): write the (m, l, acc) partials even when
+// n_split == 1, so a follow-up merge kernel can fold in an external partial
+// (mixed-device decode, attn_decode_merge_ext_kernel). 0 = unchanged.
 // PIPE=1 (NT must be 1): register double-buffered software pipeline — the
 // next tile's K AND V loads are issued before the current tile's MFMA/
 // softmax consume their buffers, so a full iteration of compute covers each
@@ -78,7 +81,8 @@ __global__ __launch_bounds__(256, 2) void attn_decode_mfma_kernel(
     float* __restrict__ part_ml,                 // (B*Hkv*nch*n_split, MAXG, 2)
     float* __restrict__ part_acc,                // (..., MAXG, D)
     int B, int Hkv, int G, int nch, int P, int maxp, int n_split, int window,
-    float scale, long q_sb, long q_sh, long out_sb, long out_sh) {
+    float scale, long q_sb, long q_sh, long out_sb, long out_sh,
+    int force_partial) {
   constexpr int NKK = D / 32;   // QK^T k-slices
   constexpr int NDT = D / 16;   // PV d-tiles
   constexpr int NPT = DKVBLK / 16;  // position tiles per KV tile
@@ -398,7 +402,7 @@ __global__ __launch_bounds__(256, 2) void attn_decode_mfma_kernel(
     }
   }
 
-  if (n_split == 1) {
+  if (n_split == 1 && !force_partial) {
     if (li < Gl) {
       const float inv = (l > 0.f) ? 1.f / l : 0.f;
       unsigned short* orow =
@@ -452,7 +456,8 @@ __global__ __launch_bounds__(256, 2) void attn_decode_wide_kernel(
     const float* __restrict__ alibi, unsigned short* __restrict__ out,
     float* __restrict__ part_ml, float* __restrict__ part_acc,
     int B, int Hkv, int G, int nch, int P, int maxp, int n_split, int window,
-    float scale, long q_sb, long q_sh, long out_sb, long out_sh) {
+    float scale, long q_sb, long q_sh, long out_sb, long out_sh,
+    int force_partial) {
   constexpr int D = 512;
   constexpr int NKK_W = 4;          // QK k-slices per wave (128 d)
   constexpr int NDT_W = 8;          // PV d-tiles per wave (128 d)
@@ -606,7 +611,7 @@ __global__ __launch_bounds__(256, 2) void attn_decode_wide_kernel(
 
   // d-partitioned output: every wave writes its own 128-d slice; (m, l) are
   // identical across waves by construction
-  if (n_split == 1) {
+  if (n_split == 1 && !force_partial) {
     if (li < Gl) {
       const float inv = (l > 0.f) ? 1.f / l : 0.f;
       unsigned short* orow =

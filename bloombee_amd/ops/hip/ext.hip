@@ -195,6 +195,14 @@ std::vector<torch::Tensor> kv_gather(torch::Tensor k_pages, torch::Tensor v_page
 // attention
 // ---------------------------------------------------------------------------
 
+// External (host-segment) partial for mixed-device decode; contract in
+// attn_decode.hip (attn_decode_merge_ext_kernel).
+struct MixedExt {
+  const float* ml;         // (B, Hq, 2)
+  const float* acc;        // (B, Hq, D)
+  const float* dev_shift;  // (Hq,) or null
+};
+
 template <int D>
 static void attn_decode_launch(const torch::Tensor& q, const torch::Tensor& kp,
                                const torch::Tensor& vp, const torch::Tensor& pt,
@@ -203,8 +211,12 @@ static void attn_decode_launch(const torch::Tensor& q, const torch::Tensor& kp,
                                torch::Tensor& pml, torch::Tensor& pacc, int B,
                                int Hkv, int G, int nch, int P, int maxp,
                                int n_split, int window, float scale, long q_off,
-                               long q_sb, long q_sh, long out_sb, long out_sh) {
+                               long q_sb, long q_sh, long out_sb, long out_sh,
+                               const MixedExt* ext = nullptr) {
   dim3 grid(B * Hkv * nch, n_split);
+  // mixed-device decode: the kernels emit partials even at n_split == 1 and
+  // the merge kernel folds in the host segment's partial
+  const int fp = ext != nullptr ? 1 : 0;
   const int maxg = (G <= 4 && nch == 1) ? 4 : 16;
   // paired-tile variant (NT=2): 2x KV bytes in flight per wave — the
   // latency-bound fix (profiles/r01_st_attention.md SQ_WAIT diagnosis).
@@ -231,33 +243,39 @@ static void attn_decode_launch(const torch::Tensor& q, const torch::Tensor& kp,
               bf_ptr(q) + q_off, bf_ptr(kp), bf_ptr(vp), pt.data_ptr<int>(),
               ctx.data_ptr<int>(), alibi_ptr, bf_ptr_mut(out),
               pml.data_ptr<float>(), pacc.data_ptr<float>(), B, Hkv, G, nch, P,
-              maxp, n_split, window, scale, q_sb, q_sh, out_sb, out_sh);
+              maxp, n_split, window, scale, q_sb, q_sh, out_sb, out_sh, fp);
     } else if (D <= 128 && pf) {
       attn_decode_mfma_kernel<D, decltype(mg)::value, 1, 1>
           <<<grid, 256, 0, cur_stream()>>>(
               bf_ptr(q) + q_off, bf_ptr(kp), bf_ptr(vp), pt.data_ptr<int>(),
               ctx.data_ptr<int>(), alibi_ptr, bf_ptr_mut(out),
               pml.data_ptr<float>(), pacc.data_ptr<float>(), B, Hkv, G, nch, P,
-              maxp, n_split, window, scale, q_sb, q_sh, out_sb, out_sh);
+              maxp, n_split, window, scale, q_sb, q_sh, out_sb, out_sh, fp);
     } else if (D <= 128 && nt2) {
       attn_decode_mfma_kernel<D, decltype(mg)::value, 2>
           <<<grid, 256, 0, cur_stream()>>>(
               bf_ptr(q) + q_off, bf_ptr(kp), bf_ptr(vp), pt.data_ptr<int>(),
               ctx.data_ptr<int>(), alibi_ptr, bf_ptr_mut(out),
               pml.data_ptr<float>(), pacc.data_ptr<float>(), B, Hkv, G, nch, P,
-              maxp, n_split, window, scale, q_sb, q_sh, out_sb, out_sh);
+              maxp, n_split, window, scale, q_sb, q_sh, out_sb, out_sh, fp);
     } else {
       attn_decode_mfma_kernel<D, decltype(mg)::value, 1>
           <<<grid, 256, 0, cur_stream()>>>(
               bf_ptr(q) + q_off, bf_ptr(kp), bf_ptr(vp), pt.data_ptr<int>(),
               ctx.data_ptr<int>(), alibi_ptr, bf_ptr_mut(out),
               pml.data_ptr<float>(), pacc.data_ptr<float>(), B, Hkv, G, nch, P,
-              maxp, n_split, window, scale, q_sb, q_sh, out_sb, out_sh);
+              maxp, n_split, window, scale, q_sb, q_sh, out_sb, out_sh, fp);
     }
   };
   if (maxg == 4) launch_mfma(std::integral_constant<int, 4>{});
   else launch_mfma(std::integral_constant<int, 16>{});
-  if (n_split > 1) {
+  if (ext != nullptr) {
+    attn_decode_merge_ext_kernel<D>
+        <<<B * Hkv * nch, maxg * 16, 0, cur_stream()>>>(
+            pml.data_ptr<float>(), pacc.data_ptr<float>(), ext->ml, ext->acc,
+            ext->dev_shift, bf_ptr_mut(out), Hkv, G, nch, maxg, n_split,
+            out_sb, out_sh);
+  } else if (n_split > 1) {
     attn_decode_combine_kernel<D>
         <<<B * Hkv * nch, maxg * 16, 0, cur_stream()>>>(
             pml.data_ptr<float>(), pacc.data_ptr<float>(), bf_ptr_mut(out),
@@ -271,7 +289,8 @@ static torch::Tensor attn_decode_core(
     const torch::Tensor& ctx_lens, const c10::optional<torch::Tensor>& alibi,
     double scale, long window, long n_split_req,
     int B, int Hq, int D, long q_off, long q_sb, long q_sh,
-    torch::Tensor out, long out_sb, long out_sh) {
+    torch::Tensor out, long out_sb, long out_sh,
+    const MixedExt* ext = nullptr) {
   const int Hkv = k_pages.size(1), P = k_pages.size(2), maxp = page_table.size(1);
   const int G = Hq / Hkv;
   TORCH_CHECK(Hq % Hkv == 0);
@@ -306,7 +325,7 @@ static torch::Tensor attn_decode_core(
   const int maxg = (G <= 4 && nch == 1) ? 4 : 16;
   auto fopt = torch::TensorOptions().device(q.device()).dtype(at::kFloat);
   torch::Tensor pml, pacc;
-  if (n_split > 1) {
+  if (n_split > 1 || ext != nullptr) {
     pml = torch::empty({(long)B * Hkv * nch * n_split, maxg, 2}, fopt);
     pacc = torch::empty({(long)B * Hkv * nch * n_split, maxg, D}, fopt);
   } else {
@@ -317,7 +336,7 @@ static torch::Tensor attn_decode_core(
     attn_decode_launch<decltype(d)::value>(
         q, k_pages, v_pages, page_table, ctx_lens, alibi_ptr, out, pml, pacc,
         B, Hkv, G, nch, P, maxp, n_split, (int)window, (float)scale, q_off,
-        q_sb, q_sh, out_sb, out_sh);
+        q_sb, q_sh, out_sb, out_sh, ext);
   };
   if (D == 128) go(std::integral_constant<int, 128>{});
   else if (D == 64) go(std::integral_constant<int, 64>{});
@@ -364,6 +383,60 @@ torch::Tensor attn_decode_qkv(torch::Tensor qkv, long Hq, torch::Tensor k_pages,
                           D, /*q_off*/ 0, (long)(Hq + 2 * Hkv) * D, (long)D,
                           out, (long)Hq * D, (long)D)
       .view({B, 1, Hq * D});
+}
+
+// Mixed-device decode: device segment on the MFMA / wide decode kernel in
+// forced-partial mode, then one merge launch that folds in the external
+// (host-prefix) partial. q is either (B, Hq, 1, D) or the fused QKV buffer
+// (B, 1, (Hq+2Hkv)*D) read in place; Hq comes from ext_ml. ctx_lens and all
+// kernel positions are LOCAL to the device pool; pos_offset (the absolute
+// position of local 0) only enters through the ALiBi shift of the device
+// partials. Returns (B, 1, Hq*D), the O-projection layout.
+torch::Tensor attn_decode_mixed(torch::Tensor q, torch::Tensor k_pages,
+                                torch::Tensor v_pages, torch::Tensor page_table,
+                                torch::Tensor ctx_lens, torch::Tensor ext_ml,
+                                torch::Tensor ext_acc, double scale, long window,
+                                long n_split_req,
+                                c10::optional<torch::Tensor> alibi,
+                                long pos_offset) {
+  CHECK_DEV(q); CHECK_BF16(q); CHECK_CONTIG(q);
+  CHECK_DEV_ALL3(k_pages, page_table, ctx_lens);
+  CHECK_DEV(ext_ml); CHECK_CONTIG(ext_ml);
+  CHECK_DEV(ext_acc); CHECK_CONTIG(ext_acc);
+  const int Hkv = k_pages.size(1), D = k_pages.size(3);
+  const int B = q.size(0);
+  TORCH_CHECK(ext_ml.scalar_type() == at::kFloat && ext_ml.dim() == 3 &&
+              ext_ml.size(0) == B && ext_ml.size(2) == 2,
+              "ext_ml must be f32 (B, Hq, 2)");
+  const int Hq = ext_ml.size(1);
+  TORCH_CHECK(ext_acc.scalar_type() == at::kFloat && ext_acc.dim() == 3 &&
+              ext_acc.size(0) == B && ext_acc.size(1) == Hq &&
+              ext_acc.size(2) == D, "ext_acc must be f32 (B, Hq, D)");
+  TORCH_CHECK(page_table.size(0) == B && ctx_lens.numel() == B,
+              "page_table / ctx_lens batch mismatch");
+  long q_sb;
+  if (q.dim() == 4) {
+    TORCH_CHECK(q.size(1) == Hq && q.size(2) == 1 && q.size(3) == D,
+                "attn_decode_mixed expects q (B, Hq, 1, D)");
+    q_sb = (long)Hq * D;
+  } else {
+    TORCH_CHECK(q.dim() == 3 && q.size(1) == 1 &&
+                q.size(2) == (long)(Hq + 2 * Hkv) * D, "bad fused qkv shape");
+    q_sb = (long)(Hq + 2 * Hkv) * D;
+  }
+  torch::Tensor shift;
+  MixedExt ext{ext_ml.data_ptr<float>(), ext_acc.data_ptr<float>(), nullptr};
+  if (alibi.has_value()) {
+    CHECK_DEV((*alibi));
+    TORCH_CHECK(alibi->scalar_type() == at::kFloat && alibi->numel() == Hq);
+    shift = (*alibi * (double)pos_offset).contiguous();
+    ext.dev_shift = shift.data_ptr<float>();
+  }
+  auto out = torch::empty({B, 1, (long)Hq * D}, q.options());
+  attn_decode_core(q, k_pages, v_pages, page_table, ctx_lens, alibi, scale,
+                   window, n_split_req, B, Hq, D, /*q_off*/ 0, q_sb, (long)D,
+                   out, (long)Hq * D, (long)D, &ext);
+  return out;
 }
 
 torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor k_pages,
@@ -853,6 +926,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wire_inflate_mt", &wire_inflate_mt);
   m.def("attn_decode", &attn_decode);
   m.def("attn_decode_qkv", &attn_decode_qkv);
+  m.def("attn_decode_mixed", &attn_decode_mixed);
   m.def("attn_prefill_qkv", &attn_prefill_qkv);
   m.def("rope_kv_write_", &rope_kv_write_);
   m.def("attn_prefill", &attn_prefill);

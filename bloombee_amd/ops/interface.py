@@ -344,15 +344,103 @@ def fuse_norm_linear_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
             and w.shape[0] % 64 == 0 and HAVE_HIP_OPS)
 
 
+# mixed-device decode on the GPU: device segment on the MFMA decode kernel
+# in forced-partial mode + one merge launch (hip_ops.attn_decode_mixed);
+# BBAMD_MIXED_KERNEL=0 falls back to the per-row torch composition
+_MIXED_KERNEL = os.environ.get("BBAMD_MIXED_KERNEL", "1") not in ("", "0")
+
+
+def _mixed_kernel_ok(D: int) -> bool:
+    # head dims the decode kernels cover (same rule as attn_decode)
+    return _MIXED_KERNEL and (D <= 256 or D == 512)
+
+
+def _attn_mixed_gpu(q_or_qkv, q4, k_pages, v_pages, page_table, ctx_lens,
+                    host_k, host_v, scale, window, alibi_slopes, n_split=0):
+    """GPU mixed-device decode. q_or_qkv: what the kernel reads q from
+    ((B, Hq, 1, D) or the fused QKV buffer); q4: a (B, Hq, 1, D) view of the
+    same q for the host copy. Returns (B, 1, Hq*D)."""
+    _require_ext()
+    B, Hq, _, D = q4.shape
+    S_host = host_k.shape[2]
+    dev = q4.device
+    al = (alibi_slopes.float().to(dev).contiguous()
+          if alibi_slopes is not None else None)
+    lo = 0
+    if window > 0:
+        # host suffix inside the window, per row (absolute positions)
+        lo = (S_host + ctx_lens.long().cpu() - window).clamp_(min=0)
+        if int(lo.min()) >= S_host:
+            # the window excludes the host prefix entirely: plain decode
+            if q_or_qkv.dim() == 3:
+                return hip_ops.attn_decode_qkv(
+                    q_or_qkv, Hq, k_pages, v_pages, page_table,
+                    ctx_lens.int(), scale, window, n_split)
+            return (hip_ops.attn_decode(q_or_qkv.contiguous(), k_pages,
+                                        v_pages, page_table, ctx_lens.int(),
+                                        scale, window, n_split, al)
+                    .permute(0, 2, 1, 3).reshape(B, 1, Hq * D))
+    # host segment: q crosses to the host, the prefix is attended there in
+    # fp32 (the point of the mode), and only the (m, l, acc) partial — one
+    # pinned buffer, one H2D copy — comes back
+    ml, acc = ref.attn_host_partial(
+        q4[:, :, 0].float().cpu(), host_k, host_v, scale, lo,
+        alibi_slopes.cpu() if alibi_slopes is not None else None)
+    n_ml = B * Hq * 2
+    stage = torch.empty(n_ml + B * Hq * D, dtype=torch.float32,
+                        pin_memory=True)
+    stage[:n_ml].copy_(ml.view(-1))
+    stage[n_ml:].copy_(acc.view(-1))
+    ext = stage.to(dev, non_blocking=True)
+    return hip_ops.attn_decode_mixed(
+        q_or_qkv, k_pages, v_pages, page_table, ctx_lens.int(),
+        ext[:n_ml].view(B, Hq, 2), ext[n_ml:].view(B, Hq, D),
+        scale, window, n_split, al, S_host)
+
+
 def attn_paged_mixed(q, k_pages, v_pages, page_table, ctx_lens,
-                     host_k, host_v, scale=None):
-    """Mixed-device decode attention: host-resident KV prefix (CPU fp32)
+                     host_k, host_v, scale=None, window: int = 0,
+                     alibi_slopes=None, n_split: int = 0):
+    """Mixed-device decode attention: host-resident KV prefix (CPU)
     + device-resident recent segment, merged with the exact log-sum-exp
     composition (ref _mixed_device_attention, pytorch_backend.py:969-1014).
-    Device-agnostic torch composition — the host segment's matmuls RUN on
-    the CPU by construction, which is the point of the mode."""
+    q: (B, Hq, 1, D); ctx_lens are LOCAL to the device pool. The host
+    segment's matmuls RUN on the CPU by construction, which is the point of
+    the mode; on GPU tensors the device segment and the merge run on the
+    decode kernels (BBAMD_MIXED_KERNEL=0: torch composition); n_split
+    (kernel path only) pins the flash-decode split count, 0 = auto."""
+    D = q.shape[-1]
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if _on_gpu(q) and _mixed_kernel_ok(D):
+        B, Hq = q.shape[0], q.shape[1]
+        out = _attn_mixed_gpu(q.contiguous(), q, k_pages, v_pages, page_table,
+                              ctx_lens, host_k, host_v, scale, window,
+                              alibi_slopes, n_split)
+        return out.view(B, 1, Hq, D).permute(0, 2, 1, 3)
     return ref.attn_paged_mixed(q, k_pages, v_pages, page_table, ctx_lens,
-                                host_k, host_v, scale)
+                                host_k, host_v, scale, window=window,
+                                alibi_slopes=alibi_slopes)
+
+
+def attn_paged_mixed_qkv(qkv, Hq: int, Hkv: int, k_pages, v_pages, page_table,
+                         ctx_lens, host_k, host_v, scale=None,
+                         window: int = 0):
+    """attn_paged_mixed reading q straight from the fused QKV buffer
+    (B, 1, (Hq+2Hkv)*D), q section already roped, the new token's K/V
+    already in the pages. Returns (B, 1, Hq*D) — the O-projection input."""
+    B, T, _ = qkv.shape
+    assert T == 1, "mixed-device path is decode-only"
+    D = k_pages.shape[3]
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    q = qkv[..., : Hq * D].view(B, T, Hq, D).permute(0, 2, 1, 3)
+    if _on_gpu(qkv) and _mixed_kernel_ok(D) and qkv.is_contiguous():
+        return _attn_mixed_gpu(qkv, q, k_pages, v_pages, page_table, ctx_lens,
+                               host_k, host_v, scale, window, None)
+    out = ref.attn_paged_mixed(q.contiguous(), k_pages, v_pages, page_table,
+                               ctx_lens, host_k, host_v, scale, window=window)
+    return out.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
 
 
 def moe_gemm_grouped(A: torch.Tensor, W: torch.Tensor, off: torch.Tensor,

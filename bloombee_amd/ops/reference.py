@@ -349,6 +349,49 @@ def attn_paged_topk(
     return out
 
 
+def attn_host_partial(
+    q_cpu: torch.Tensor,
+    host_k: torch.Tensor, host_v: torch.Tensor,
+    scale: float,
+    lo=0,
+    alibi_slopes: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Host segment of mixed-device decode attention as ONE softmax partial
+    per query head, batched fp32 on the CPU (no per-row Python loop).
+
+    q_cpu: (B, Hq, D) CPU; host_k/host_v: (B, Hkv, S, D) CPU — absolute
+    positions [0, S). lo: int or (B,) — positions < lo[b] are masked (the
+    sliding-window suffix). alibi_slopes: (Hq,) — bias slope_h * j with j the
+    ABSOLUTE position.
+
+    Returns the external partial in the merge kernel's contract
+    (ops/hip/attn_decode.hip attn_decode_merge_ext_kernel), natural-log
+    units: ml (B, Hq, 2) = [max score, sum exp(s - max)], acc (B, Hq, D) =
+    sum exp(s - max) * v, un-normalised. Rows with no live position carry
+    l == 0 (m = 0, acc = 0) and are skipped by the merge."""
+    B, Hq, D = q_cpu.shape
+    Hkv, S = host_k.shape[1], host_k.shape[2]
+    G = Hq // Hkv
+    qf = q_cpu.float().view(B, Hkv, G, D)
+    s = torch.einsum("bkgd,bkcd->bkgc", qf, host_k.float()) * scale
+    pos = torch.arange(S)
+    if alibi_slopes is not None:
+        s = s + (alibi_slopes.float().cpu().view(1, Hkv, G, 1)
+                 * pos.float().view(1, 1, 1, S))
+    live = None
+    if not (isinstance(lo, int) and lo <= 0):
+        lo_t = torch.as_tensor(lo).cpu().long().reshape(-1, 1)   # (B|1, 1)
+        live = (pos.view(1, S) >= lo_t).expand(B, S)             # (B, S)
+        s = s.masked_fill(~live.view(B, 1, 1, S), float("-inf"))
+    m = s.max(-1, keepdim=True).values
+    m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))   # empty rows
+    p = torch.exp(s - m)
+    l = p.sum(-1)
+    acc = torch.einsum("bkgc,bkcd->bkgd", p, host_v.float())
+    ml = torch.stack([m.squeeze(-1), l], dim=-1).reshape(B, Hq, 2)
+    return ml.contiguous(), acc.reshape(B, Hq, D).contiguous()
+
+
 def attn_paged_mixed(
     q: torch.Tensor,
     k_pages: torch.Tensor, v_pages: torch.Tensor,
@@ -356,6 +399,8 @@ def attn_paged_mixed(
     ctx_lens: torch.Tensor,
     host_k: torch.Tensor, host_v: torch.Tensor,
     scale: Optional[float] = None,
+    window: int = 0,
+    alibi_slopes: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Mixed-device decode attention (parity: reference
     pytorch_backend.py:969-1014 `_mixed_device_attention` — KV split into a
@@ -366,6 +411,13 @@ def attn_paged_mixed(
     The paged pool holds positions [S_host, S_host + ctx_lens[b]).
     q: (B, Hq, 1, D) on any device. Merge is exact (log-sum-exp), so the
     result equals dense attention over the concatenated cache.
+
+    window > 0: sliding window over ABSOLUTE positions — the query at
+    S_host + ctx - 1 sees the last `window` positions, i.e. the device
+    suffix [max(0, ctx - window), ctx) plus the host suffix
+    [max(0, S_host + ctx - window), S_host) (possibly empty).
+    alibi_slopes (Hq,): bias slope_h * j with j absolute — host positions as
+    they are, device positions shifted by S_host.
     """
     B, Hq, Tq, D = q.shape
     assert Tq == 1, "mixed-device path is decode-only"
@@ -374,31 +426,39 @@ def attn_paged_mixed(
     S_host = host_k.shape[2]
     if scale is None:
         scale = 1.0 / math.sqrt(D)
+    ctx_host = [int(c) for c in ctx_lens.tolist()]
+    lo = 0
+    if window > 0:
+        lo = torch.tensor([max(0, S_host + c - window) for c in ctx_host])
+    # host segment on CPU (fp32), whole batch at once
+    ml_h, o_h_all = attn_host_partial(q[:, :, 0].float().cpu(), host_k, host_v,
+                                      scale, lo, alibi_slopes)
+    neg_inf = torch.full((), float("-inf"))
+    m_h_all = torch.where(ml_h[..., 1] > 0, ml_h[..., 0], neg_inf)
+    al = (alibi_slopes.float().to(q.device).view(-1, 1)
+          if alibi_slopes is not None else None)
     out = torch.empty_like(q)
     for b in range(B):
         qf = q[b, :, 0].float()  # (Hq, D)
-        # host segment on CPU (fp32)
-        qc = qf.cpu()
-        kh = host_k[b].float().repeat_interleave(G, dim=0)  # (Hq, S_host, D)
-        vh = host_v[b].float().repeat_interleave(G, dim=0)
-        s_h = torch.einsum("hd,hcd->hc", qc, kh) * scale
-        m_h = s_h.max(-1, keepdim=True).values
-        p_h = torch.exp(s_h - m_h)
-        l_h = p_h.sum(-1)                                   # (Hq,)
-        o_h = torch.einsum("hc,hcd->hd", p_h, vh)
         # device-resident recent segment via the paged pool
-        ctx = int(ctx_lens[b])
+        ctx = ctx_host[b]
         k, v = kv_gather(k_pages, v_pages, page_table, ctx, b)
         kg = k.float().repeat_interleave(G, dim=0)
         vg = v.float().repeat_interleave(G, dim=0)
         s_d = torch.einsum("hd,hcd->hc", qf, kg) * scale
+        jl = torch.arange(ctx, device=q.device)
+        if al is not None:
+            s_d = s_d + al * (jl + S_host).float().view(1, ctx)
+        if window > 0:
+            s_d = s_d.masked_fill((jl < ctx - window).view(1, ctx),
+                                  float("-inf"))
         m_d = s_d.max(-1, keepdim=True).values
         p_d = torch.exp(s_d - m_d)
         l_d = p_d.sum(-1)
         o_d = torch.einsum("hc,hcd->hd", p_d, vg)
         # exact merge of the two partial softmaxes
-        m_hd, m_dd = m_h[:, 0].to(q.device), m_d[:, 0]
-        o_hd, l_hd = o_h.to(q.device), l_h.to(q.device)
+        m_hd, m_dd = m_h_all[b].to(q.device), m_d[:, 0]
+        o_hd, l_hd = o_h_all[b].to(q.device), ml_h[b, :, 1].to(q.device)
         m = torch.maximum(m_hd, m_dd)
         c_h = torch.exp(m_hd - m).unsqueeze(-1)
         c_d = torch.exp(m_dd - m).unsqueeze(-1)

@@ -1,0 +1,150 @@
+"""Mixed-device decode (host KV prefix + device recent segment) for every
+family: op-level exactness with sliding windows and ALiBi, and block-level
+hidden-state equality between a never-swapped session and one that went
+through swap_out(); swap_in_as_prefix(). CPU only."""
+import pytest
+import torch
+
+from bloombee_amd import ops
+from bloombee_amd.ops import reference as ref
+from mixed_device_scenario import FAMILIES, decode_hidden, make_engine
+
+
+def split_cache(kp, vp, pt, S_host, ctx_dev, P):
+    """Split a dense paged cache (row b holds S_host + ctx_dev[b] positions)
+    into host tensors (B, Hkv, S_host, D) and a second paged pool holding
+    the remaining positions at pool-local indices."""
+    B = pt.shape[0]
+    Hkv, D = kp.shape[1], kp.shape[3]
+    hk = torch.empty(B, Hkv, S_host, D, dtype=kp.dtype)
+    hv = torch.empty(B, Hkv, S_host, D, dtype=kp.dtype)
+    maxp = max(ctx_dev) // P + 1
+    kp2 = torch.zeros(B * maxp, Hkv, P, D, dtype=kp.dtype)
+    vp2 = torch.zeros(B * maxp, Hkv, D, P, dtype=kp.dtype)
+    pt2 = torch.arange(B * maxp, dtype=torch.int32).view(B, maxp)
+    for b in range(B):
+        k, v = ref.kv_gather(kp, vp, pt, S_host + ctx_dev[b], b)
+        hk[b], hv[b] = k[:, :S_host], v[:, :S_host]
+        for t in range(ctx_dev[b]):
+            pg = pt2[b, t // P]
+            kp2[pg, :, t % P] = k[:, S_host + t]
+            vp2[pg, :, :, t % P] = v[:, S_host + t]
+    return hk, hv, kp2, vp2, pt2
+
+
+@pytest.mark.parametrize("S_host,S_dev,window,alibi", [
+    (48, 33, 0, True),
+    (48, 1, 0, True),
+    (48, 17, 40, False),   # partial host suffix inside the window
+    (48, 17, 8, False),    # window inside the device segment: host excluded
+    (48, 17, 17, False),   # window == device segment: host just excluded
+    (48, 17, 18, True),    # one host position in the window
+])
+def test_mixed_attention_window_alibi_exact(S_host, S_dev, window, alibi):
+    """ref.attn_paged_mixed == dense ref.attn_paged over the concatenated
+    cache, fp32, with sliding window and ALiBi on absolute positions."""
+    torch.manual_seed(1)
+    B, Hq, Hkv, D, P = 2, 8, 2, 32, 16
+    S = S_host + S_dev
+    maxp = S // P + 1
+    kp = torch.randn(B * maxp, Hkv, P, D) * 0.3
+    vp = torch.randn(B * maxp, Hkv, D, P) * 0.3
+    pt = torch.arange(B * maxp, dtype=torch.int32).view(B, maxp)
+    q = torch.randn(B, Hq, 1, D) * 0.3
+    slopes = ops.alibi_slopes_for(Hq) if alibi else None
+    ctx = torch.full((B,), S, dtype=torch.int32)
+    dense = ref.attn_paged(q, kp, vp, pt, ctx.long() - 1,
+                           sliding_window=window if window > 0 else None,
+                           alibi_slopes=slopes)
+    hk, hv, kp2, vp2, pt2 = split_cache(kp, vp, pt, S_host, [S_dev] * B, P)
+    ctx_dev = torch.full((B,), S_dev, dtype=torch.int32)
+    mixed = ref.attn_paged_mixed(q, kp2, vp2, pt2, ctx_dev, hk, hv,
+                                 window=window, alibi_slopes=slopes)
+    err = (dense - mixed).abs().max()
+    print(f"S_dev={S_dev} window={window} alibi={alibi} max err {err:.3e}")
+    assert torch.allclose(dense, mixed, atol=1e-4), err
+    # the public dispatch takes the same path on CPU tensors
+    via_ops = ops.attn_paged_mixed(q, kp2, vp2, pt2, ctx_dev, hk, hv,
+                                   window=window, alibi_slopes=slopes)
+    assert torch.equal(via_ops, mixed)
+
+
+def test_host_partial_contract():
+    """attn_host_partial returns natural-log (m, l, acc) per query head;
+    rows whose window excludes every host position carry l == 0."""
+    torch.manual_seed(2)
+    B, Hq, Hkv, S, D = 3, 4, 2, 10, 8
+    q = torch.randn(B, Hq, D)
+    hk, hv = torch.randn(B, Hkv, S, D), torch.randn(B, Hkv, S, D)
+    lo = torch.tensor([0, 7, 10])
+    ml, acc = ref.attn_host_partial(q, hk, hv, 0.5, lo)
+    assert ml.shape == (B, Hq, 2) and acc.shape == (B, Hq, D)
+    G = Hq // Hkv
+    for b in range(B):
+        for h in range(Hq):
+            s = (hk[b, h // G, int(lo[b]):] @ q[b, h]) * 0.5
+            if s.numel() == 0:
+                assert ml[b, h, 1] == 0 and acc[b, h].abs().max() == 0
+                continue
+            p = torch.exp(s - s.max())
+            assert torch.allclose(ml[b, h, 0], s.max(), atol=1e-6)
+            assert torch.allclose(ml[b, h, 1], p.sum(), atol=1e-5)
+            assert torch.allclose(acc[b, h], p @ hv[b, h // G, int(lo[b]):],
+                                  atol=1e-5)
+
+
+def assert_hidden_match(dense, mixed):
+    """Bit equality is expected; a bf16 rounding flipped by fp32
+    reassociation is tolerated up to 2**-8 of the dense run's magnitude."""
+    diff = (dense - mixed).abs().max().item()
+    peak = dense.abs().max().item()
+    ndiff = int((dense != mixed).sum())
+    print(f"max|dense| {peak:.4g}  max|diff| {diff:.4g}  "
+          f"{ndiff} of {dense.numel()} elements differ")
+    assert diff <= 2 ** -8 * peak, (diff, peak)
+
+
+@pytest.mark.parametrize("model", FAMILIES)
+def test_mixed_device_decode_hidden_states(model):
+    """Decode hidden states of a host-prefixed session equal the
+    never-swapped run's. gemma4-tiny (sliding_window 8) crosses from "host
+    suffix inside the window" to "host excluded" within the 12 steps."""
+    eng = make_engine(model)
+    dense = decode_hidden(eng, swapped=False)
+    mixed = decode_hidden(eng, swapped=True)
+    assert_hidden_match(dense, mixed)
+
+
+def test_mixed_attn_on_backend_bloom():
+    """mixed_attn="on" through the real backend for a non-rope family: the
+    swapped session decodes with a host prefix and returns the hidden states
+    of a never-swapped session."""
+    from bloombee_amd.config import (KVConfig, RuntimeConfig, get_config,
+                                     set_config)
+    from bloombee_amd.models.base import resolve_config
+    from bloombee_amd.server.backend import StackBackend
+
+    cfg = resolve_config("bloom-tiny")
+    gen = torch.Generator().manual_seed(5)
+    h0 = (torch.randn(2, 40, cfg.hidden_size, generator=gen) * 0.1).to(cfg.dtype)
+    steps = (torch.randn(12, 2, 1, cfg.hidden_size, generator=gen)
+             * 0.1).to(cfg.dtype)
+    old_cfg = get_config()
+    set_config(RuntimeConfig(kv=KVConfig(mixed_attn="on")))
+    be = StackBackend(cfg, 0, 2, device="cpu", seed=0, kv_max_tokens=16 * 16)
+    try:
+        runs = {}
+        for name in ("dense", "mixed"):
+            be.open_session(name, 2, 64)
+            be.inference_step(name, h0, 0)
+            handle = be.session_handle(name)
+            if name == "mixed":
+                handle.swap_out()
+            outs = [be.inference_step(name, steps[t], 40 + t).float().cpu()
+                    for t in range(12)]
+            assert handle.pos_offset == (40 if name == "mixed" else 0)
+            runs[name] = torch.stack(outs)
+            be.close_session(name)
+        assert_hidden_match(runs["dense"], runs["mixed"])
+    finally:
+        set_config(old_cfg)
