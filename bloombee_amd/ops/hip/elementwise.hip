@@ -202,6 +202,13 @@ __global__ void gelu_kernel(const unsigned short* __restrict__ x,
     }
     store_bf16x8(out + idx * 8, o);
   }
+  // scalar tail for n % 8 != 0 (the op is exposed as general)
+  for (long i = nvec * 8 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
+       i += (long)gridDim.x * blockDim.x) {
+    const float v = bf2f(x[i]);
+    const float t = tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v));
+    out[i] = f2bf(0.5f * v * (1.f + t));
+  }
 }
 
 // residual add: out = a + b (bf16), used where no norm fusion applies
@@ -218,6 +225,10 @@ __global__ void add_kernel(const unsigned short* __restrict__ a,
     for (int j = 0; j < 8; ++j) o[j] = va[j] + vb[j];
     store_bf16x8(out + idx * 8, o);
   }
+  // scalar tail for n % 8 != 0
+  for (long i = nvec * 8 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
+       i += (long)gridDim.x * blockDim.x)
+    out[i] = f2bf(bf2f(a[i]) + bf2f(b[i]));
 }
 
 // ---------------------------------------------------------------------------

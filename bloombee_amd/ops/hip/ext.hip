@@ -138,16 +138,19 @@ torch::Tensor gelu_tanh(torch::Tensor x) {
   CHECK_DEV(x); CHECK_BF16(x); CHECK_CONTIG(x);
   auto out = torch::empty_like(x);
   const long nvec = x.numel() / 8;
-  const int grid = (int)std::min<long>((nvec + 255) / 256, 2048);
+  // >= 1 block so the scalar tail (numel % 8) runs when numel < 8
+  const int grid = (int)std::max<long>(1, std::min<long>((nvec + 255) / 256, 2048));
   gelu_kernel<<<grid, 256, 0, cur_stream()>>>(bf_ptr(x), bf_ptr_mut(out), x.numel());
   return out;
 }
 
 torch::Tensor add_bf16(torch::Tensor a, torch::Tensor b) {
   CHECK_DEV(a); CHECK_BF16(a); CHECK_CONTIG(a); CHECK_CONTIG(b);
+  CHECK_DEV(b); CHECK_BF16(b);
+  TORCH_CHECK(b.numel() == a.numel(), "add_bf16: numel mismatch");
   auto out = torch::empty_like(a);
   const long nvec = a.numel() / 8;
-  const int grid = (int)std::min<long>((nvec + 255) / 256, 2048);
+  const int grid = (int)std::max<long>(1, std::min<long>((nvec + 255) / 256, 2048));
   add_kernel<<<grid, 256, 0, cur_stream()>>>(bf_ptr(a), bf_ptr(b), bf_ptr_mut(out),
                                              a.numel());
   return out;
@@ -632,7 +635,9 @@ torch::Tensor gemm_w4(torch::Tensor A, torch::Tensor Wq, torch::Tensor scale,
   // extension was measured and REJECTED for dispatch: amortizing the
   // dequant over rows loses to the split-K MFMA form (M4 down-proj 131 us
   // vs ~13 — the per-lane 4 B A loads scale with M and dominate); the
-  // kernel keeps MROWS for completeness (parity-tested).
+  // kernel keeps MROWS as a template parameter, but only MROWS == 1 is
+  // reachable from this dispatch: the MROWS > 1 instantiations are not
+  // run by any test.
   if (M == 1 && K % 2048 == 0 && K / 2048 <= 7) {
     const int rpw = 4;
     dim3 gv((N / rpw + 3) / 4);

@@ -55,8 +55,9 @@ DEVINL half8 dq8_q4_f16(unsigned int c, half2v sc2, half2v zp2) {
 // ---------------------------------------------------------------------------
 // MROWS (1..4): batch rows sharing one code stream — the dequant (the
 // issue-bound part, see profiles/r02 §4 PMC) is amortized over MROWS
-// v_dot2 chains, so M<=4 runs near the M=1 byte rate instead of falling
-// back to the 2.25 TB/s MFMA form (ROUND3 item 4).
+// v_dot2 chains (ROUND3 item 4). Measured slower than the split-K MFMA form
+// and NOT dispatched: gemm_w4 in ext.hip launches MROWS == 1 only, so the
+// MROWS > 1 instantiations are compiled but run by no caller and no test.
 template <int NLOADS, int MROWS = 1>  // NLOADS = K / 2048
 __global__ __launch_bounds__(256) void gemm_w4_gemv_kernel(
     const _Float16* __restrict__ A,           // (MROWS, K) fp16

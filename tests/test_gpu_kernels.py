@@ -669,9 +669,11 @@ def test_qwen3_block_fused_norm_matches_unfused():
 
 
 @pytest.mark.gpu
-def test_gemm_w4_gemv_small_m_parity():
-    """W4 GEMV M<=4 path (dequant amortized over rows) vs dequantized
-    F.linear reference."""
+def test_gemm_w4_small_m_parity():
+    """linear_w4 at M = 1..4 vs the dequantized F.linear reference. Only
+    M == 1 runs the GEMV (gemm_w4 in ext.hip dispatches it for M == 1
+    alone); M = 2..4 exercise the split-K MFMA form. The GEMV's MROWS > 1
+    instantiations are not reachable from dispatch and not tested."""
     torch.manual_seed(17)
     for M in (1, 2, 3, 4):
         for N, K in [(512, 2048), (1024, 4096), (256, 14336)]:
