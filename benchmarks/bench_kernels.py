@@ -95,6 +95,79 @@ def bench_attn_mixed():
           f"{t_old/t_mix:.1f}x its device time)")
 
 
+def bench_attn_sparse():
+    """Top-k sparse decode (ops.set_attn_sparsity): the attn_sparse.hip kernel
+    path against the per-row torch composition it replaces
+    (ref.attn_paged_topk as it stands, stable sort included, on the same
+    device tensors: one host sync per batch row) and against dense
+    attn_decode, per K fill:
+
+      random   K ~ N(0,1): the kept set of every head is scattered
+      peaked   K aligned with the group's queries at positions 0..3 and the
+               last 256 (sinks + recent tokens); the other 252 kept positions
+               of each head stay scattered
+      clustered  the same with the last 508 positions, so the whole kept set
+               (kkeep = 512) sits in 33 pages
+
+    and reports the share of (row, kv head, page) tiles in which none of the
+    G heads kept a position: the V loads the kernel skips."""
+    from bloombee_amd.ops import hip_ops
+    B, Hq, Hkv, ctx, D, P, sparsity = 32, 32, 8, 2048, 128, 16, 0.25
+    G = Hq // Hkv
+    maxp = ctx // P
+    scale = 1.0 / math.sqrt(D)
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    rn = lambda *sh: torch.randn(*sh, generator=gen, device=DEV)
+    q = rn(B, Hq, 1, D).to(torch.bfloat16)
+    v = rn(B, Hkv, ctx, D)
+    pt = torch.arange(B * maxp, dtype=torch.int32, device=DEV).reshape(B, maxp)
+    ctx_l = torch.full((B,), ctx, dtype=torch.int32, device=DEV)
+    to_pages = lambda x: torch.cat([
+        x.view(B, Hkv, maxp, P, D).permute(0, 2, 1, 3, 4)
+        .reshape(B * maxp, Hkv, P, D),
+        torch.zeros(1, Hkv, P, D, device=DEV)]).to(torch.bfloat16).contiguous()
+    vp = to_pages(v).transpose(2, 3).contiguous()
+    kkeep = max(1, min(ctx, math.ceil(sparsity * ctx)))
+    tag = f"B{B} Hq{Hq}/{Hkv} ctx{ctx} D{D} s={sparsity}"
+    for fill, recent in (("random", 0), ("peaked", 256), ("clustered", 508)):
+        k = rn(B, Hkv, ctx, D)
+        if recent:
+            qg = q.float().view(B, Hkv, G, D).sum(2)           # (B, Hkv, D)
+            hot = torch.cat([torch.arange(4, device=DEV),
+                             torch.arange(ctx - recent, ctx, device=DEV)])
+            k[:, :, hot] += 0.5 * qg[:, :, None, :]
+        kp = to_pages(k)
+        # kept set in torch (fp32 scores of the bf16 pool values)
+        kf = kp[:-1].float().view(B, maxp, Hkv, P, D).permute(0, 2, 1, 3, 4) \
+            .reshape(B, Hkv, ctx, D)
+        sc_ = torch.einsum("bhgd,bhcd->bhgc", q.float().view(B, Hkv, G, D),
+                           kf) * scale
+        idx = sc_.topk(kkeep, dim=-1).indices
+        kept = torch.zeros_like(sc_, dtype=torch.bool).scatter_(-1, idx, True)
+        touched = kept.view(B, Hkv, G, maxp, P).any(dim=4).any(dim=2)
+        skipped = 1.0 - float(touched.float().mean())
+
+        out_k = hip_ops.attn_decode_sparse(q, kp, vp, pt, ctx_l, sparsity,
+                                           scale, None)
+        out_c = ref.attn_paged_topk(q, kp, vp, pt, ctx_l, sparsity, scale)
+        diff = float((out_k.float() - out_c.float()).abs().max())
+        t_dense = timeit(lambda: ops.attn_decode(q, kp, vp, pt, ctx_l))
+        t_kern = timeit(lambda: hip_ops.attn_decode_sparse(
+            q, kp, vp, pt, ctx_l, sparsity, scale, None))
+        t_comp = timeit(lambda: ref.attn_paged_topk(
+            q, kp, vp, pt, ctx_l, sparsity, scale), iters=5, warmup=1)
+        t_dense2 = timeit(lambda: ops.attn_decode(q, kp, vp, pt, ctx_l))
+        t_kern2 = timeit(lambda: hip_ops.attn_decode_sparse(
+            q, kp, vp, pt, ctx_l, sparsity, scale, None))
+        print(f"attn_sparse {tag} K={fill}: page tiles skipped "
+              f"{100 * skipped:5.1f}%  max|kernel - composition| {diff:.4f}")
+        print(f"  kernel       {t_kern*1e6:9.1f} us (repeat {t_kern2*1e6:.1f})")
+        print(f"  composition  {t_comp*1e6:9.1f} us  "
+              f"({t_comp/t_kern:.1f}x the kernel)")
+        print(f"  dense decode {t_dense*1e6:9.1f} us (repeat {t_dense2*1e6:.1f})"
+              f"  kernel / dense = {t_kern/t_dense:.2f}")
+
+
 def bench_attn_prefill():
     for B, Hq, Hkv, T, D in [(32, 32, 8, 512, 128), (8, 32, 8, 2048, 128)]:
         P = 16
@@ -188,6 +261,7 @@ def bench_gemm_norm():
 ALL = {
     "attn_decode": bench_attn_decode,
     "attn_mixed": bench_attn_mixed,
+    "attn_sparse": bench_attn_sparse,
     "attn_prefill": bench_attn_prefill,
     "kv_stream": bench_kv_stream,
     "norms": bench_norms,

@@ -15,6 +15,7 @@
 #include "kvcache.hip"
 #include "attn_decode.hip"
 #include "attn_decode_mfma.hip"
+#include "attn_sparse.hip"
 #include "attn_prefill.hip"
 #include "gemm_skinny.hip"
 #include "moe_gemm.hip"
@@ -386,6 +387,134 @@ torch::Tensor attn_decode_qkv(torch::Tensor qkv, long Hq, torch::Tensor k_pages,
                           D, /*q_off*/ 0, (long)(Hq + 2 * Hkv) * D, (long)D,
                           out, (long)Hq * D, (long)D)
       .view({B, 1, Hq * D});
+}
+
+// ---------------------------------------------------------------------------
+// Top-k sparse decode (attn_sparse.hip): scores -> select -> P.V -> combine,
+// four launches on the current stream, no host sync, ctx_lens never read on
+// the host (kkeep is computed on the device, so the call is graph-capturable).
+template <int D>
+static void attn_sparse_launch(const torch::Tensor& q, const torch::Tensor& kp,
+                               const torch::Tensor& vp, const torch::Tensor& pt,
+                               const torch::Tensor& ctx, const float* alibi_ptr,
+                               torch::Tensor& out, torch::Tensor& ws,
+                               torch::Tensor& lsum, torch::Tensor& pacc, int B,
+                               int Hkv, int G, int nch, int maxp, int N,
+                               int n_split, double sparsity, float scale,
+                               long q_off, long q_sb, long q_sh, long out_sb,
+                               long out_sh) {
+  const int BH = B * Hkv * nch;
+  attn_sparse_scores_kernel<D>
+      <<<dim3(BH, (N + 127) / 128), 256, 0, cur_stream()>>>(
+          bf_ptr(q) + q_off, bf_ptr(kp), pt.data_ptr<int>(),
+          ctx.data_ptr<int>(), alibi_ptr, ws.data_ptr<float>(), Hkv, G, nch,
+          maxp, N, scale, q_sb, q_sh);
+  attn_sparse_select_kernel<<<B * Hkv * G, 256, 0, cur_stream()>>>(
+      ws.data_ptr<float>(), lsum.data_ptr<float>(), ctx.data_ptr<int>(),
+      Hkv * G, N, sparsity);
+  attn_sparse_pv_kernel<D><<<dim3(BH, n_split), 256, 0, cur_stream()>>>(
+      ws.data_ptr<float>(), bf_ptr(vp), pt.data_ptr<int>(),
+      ctx.data_ptr<int>(), pacc.data_ptr<float>(), Hkv, G, nch, maxp, N,
+      n_split);
+  attn_sparse_combine_kernel<<<BH, 256, 0, cur_stream()>>>(
+      pacc.data_ptr<float>(), lsum.data_ptr<float>(), bf_ptr_mut(out), Hkv, G,
+      nch, D, n_split, out_sb, out_sh);
+}
+
+static torch::Tensor attn_sparse_core(
+    const torch::Tensor& q, const torch::Tensor& k_pages,
+    const torch::Tensor& v_pages, const torch::Tensor& page_table,
+    const torch::Tensor& ctx_lens, const c10::optional<torch::Tensor>& alibi,
+    double sparsity, double scale, int B, int Hq, int D, long q_off, long q_sb,
+    long q_sh, torch::Tensor out, long out_sb, long out_sh) {
+  CHECK_BF16(k_pages); CHECK_CONTIG(k_pages);
+  CHECK_BF16(v_pages); CHECK_CONTIG(v_pages);
+  CHECK_CONTIG(page_table); CHECK_CONTIG(ctx_lens);
+  TORCH_CHECK(k_pages.dim() == 4 && v_pages.dim() == 4 && page_table.dim() == 2,
+              "bad KV pool / page table rank");
+  const int Hkv = k_pages.size(1), P = k_pages.size(2);
+  const int maxp = page_table.size(1);
+  TORCH_CHECK(P == 16, "sparse decode is written for page size 16, got ", P);
+  TORCH_CHECK(k_pages.size(3) == D && v_pages.size(0) == k_pages.size(0) &&
+              v_pages.size(1) == Hkv && v_pages.size(2) == D &&
+              v_pages.size(3) == P, "K (np,Hkv,P,D) / V (np,Hkv,D,P) mismatch");
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "Hq must be a multiple of Hkv");
+  TORCH_CHECK(page_table.scalar_type() == at::kInt &&
+              ctx_lens.scalar_type() == at::kInt,
+              "page_table / ctx_lens must be int32");
+  TORCH_CHECK(page_table.size(0) == B && ctx_lens.numel() == B,
+              "page_table / ctx_lens batch mismatch");
+  TORCH_CHECK(B > 0 && maxp > 0, "empty batch or page table");
+  const int G = Hq / Hkv;
+  const int nch = (G + 15) / 16;  // MQA chunks (falcon G=71 -> 5)
+  const float* alibi_ptr = nullptr;
+  if (alibi.has_value()) {
+    TORCH_CHECK(alibi->scalar_type() == at::kFloat && alibi->numel() == Hq &&
+                alibi->is_contiguous());
+    alibi_ptr = alibi->data_ptr<float>();
+  }
+  const int N = maxp * P;
+  // P.V splits: ~1024 workgroups, and at least 256 positions per split
+  const int n_split = (int)std::max<long>(
+      1, std::min<long>(std::min<long>(32, N / 256),
+                        1024 / std::max(1, B * Hkv * nch)));
+  auto fopt = torch::TensorOptions().device(q.device()).dtype(at::kFloat);
+  auto ws = torch::empty({B, Hq, N}, fopt);
+  auto lsum = torch::empty({B, Hq}, fopt);
+  auto pacc = torch::empty({(long)B * Hkv * nch * n_split, 16, D}, fopt);
+  auto go = [&](auto d) {
+    attn_sparse_launch<decltype(d)::value>(
+        q, k_pages, v_pages, page_table, ctx_lens, alibi_ptr, out, ws, lsum,
+        pacc, B, Hkv, G, nch, maxp, N, n_split, sparsity, (float)scale, q_off,
+        q_sb, q_sh, out_sb, out_sh);
+  };
+  if (D == 128) go(std::integral_constant<int, 128>{});
+  else if (D == 64) go(std::integral_constant<int, 64>{});
+  else if (D == 256) go(std::integral_constant<int, 256>{});
+  else TORCH_CHECK(false, "sparse decode supports head_dim 64/128/256, got ", D);
+  return out;
+}
+
+torch::Tensor attn_decode_sparse(torch::Tensor q, torch::Tensor k_pages,
+                                 torch::Tensor v_pages, torch::Tensor page_table,
+                                 torch::Tensor ctx_lens, double sparsity,
+                                 double scale,
+                                 c10::optional<torch::Tensor> alibi) {
+  CHECK_DEV(q); CHECK_BF16(q); CHECK_CONTIG(q);
+  CHECK_DEV_ALL3(k_pages, page_table, ctx_lens);
+  CHECK_DEV(v_pages);
+  if (alibi.has_value()) CHECK_DEV((*alibi));
+  TORCH_CHECK(q.dim() == 4 && q.size(2) == 1,
+              "attn_decode_sparse expects (B, Hq, 1, D)");
+  const int B = q.size(0), Hq = q.size(1), D = q.size(3);
+  auto out = torch::empty({B, Hq, 1, D}, q.options());
+  return attn_sparse_core(q, k_pages, v_pages, page_table, ctx_lens, alibi,
+                          sparsity, scale, B, Hq, D, /*q_off*/ 0, (long)Hq * D,
+                          (long)D, out, (long)Hq * D, (long)D);
+}
+
+// Fused-QKV sparse decode: q read in place from (B, 1, (Hq+2Hkv)*D), out
+// (B, 1, Hq*D) in the O-projection layout.
+torch::Tensor attn_decode_sparse_qkv(torch::Tensor qkv, long Hq,
+                                     torch::Tensor k_pages,
+                                     torch::Tensor v_pages,
+                                     torch::Tensor page_table,
+                                     torch::Tensor ctx_lens, double sparsity,
+                                     double scale) {
+  CHECK_DEV(qkv); CHECK_BF16(qkv); CHECK_CONTIG(qkv);
+  CHECK_DEV_ALL3(k_pages, page_table, ctx_lens);
+  CHECK_DEV(v_pages);
+  TORCH_CHECK(k_pages.dim() == 4, "bad KV pool rank");
+  const int Hkv = k_pages.size(1);
+  const int D = k_pages.size(3);
+  const int B = qkv.size(0);
+  TORCH_CHECK(Hq > 0 && qkv.dim() == 3 && qkv.size(1) == 1 &&
+              qkv.size(2) == (Hq + 2 * Hkv) * D, "bad fused qkv shape");
+  auto out = torch::empty({B, 1, Hq * D}, qkv.options());
+  return attn_sparse_core(qkv, k_pages, v_pages, page_table, ctx_lens,
+                          c10::nullopt, sparsity, scale, B, (int)Hq, D,
+                          /*q_off*/ 0, (long)(Hq + 2 * Hkv) * D, (long)D, out,
+                          (long)Hq * D, (long)D);
 }
 
 // Mixed-device decode: device segment on the MFMA / wide decode kernel in
@@ -932,6 +1061,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode", &attn_decode);
   m.def("attn_decode_qkv", &attn_decode_qkv);
   m.def("attn_decode_mixed", &attn_decode_mixed);
+  m.def("attn_decode_sparse", &attn_decode_sparse);
+  m.def("attn_decode_sparse_qkv", &attn_decode_sparse_qkv);
   m.def("attn_prefill_qkv", &attn_prefill_qkv);
   m.def("rope_kv_write_", &rope_kv_write_);
   m.def("attn_prefill", &attn_prefill);

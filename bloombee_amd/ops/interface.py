@@ -128,9 +128,39 @@ def set_attn_sparsity(frac: float) -> None:
     """Enable top-k sparse decode attention globally (parity: reference
     Policy.attn_sparsity — a server-wide policy knob, not per-call). frac
     is the fraction of cache positions whose V rows participate; 1.0
-    restores exact dense attention."""
+    restores exact dense attention.
+
+    Per query head the ceil(frac * ctx) highest-scoring positions are kept
+    (ties at the threshold go to the lowest positions) and the softmax is
+    renormalised over them; ref.attn_paged_topk is the definition. It applies
+    to single-token decode through attn_decode / attn_paged (Tq == 1) and
+    attn_paged_qkv (T == 1), i.e. to every model family, ALiBi included.
+    Device tensors run the gfx950 kernels (attn_sparse.hip: no host sync,
+    graph-capturable) for head dims 64 / 128 / 256 at page size 16, and the
+    per-row torch composition otherwise; CPU tensors run the reference.
+
+    Dense stays dense everywhere else:
+      * frac == 1.0 (the default),
+      * sliding-window layers (window > 0),
+      * prefill and tree / speculative verify (Tq > 1 or a tree_mask),
+      * mixed-device decode with a host-resident prefix
+        (attn_paged_mixed / attn_paged_mixed_qkv).
+    """
     global _attn_sparsity
     _attn_sparsity = float(frac)
+
+
+# top-k sparse decode on the GPU: attn_sparse.hip (scores / select / P.V);
+# BBAMD_SPARSE_KERNEL=0 falls back to the per-row torch composition
+# (ref.attn_paged_topk on the device tensors: one host sync per batch row)
+_SPARSE_KERNEL = os.environ.get("BBAMD_SPARSE_KERNEL", "1") not in ("", "0")
+
+
+def _sparse_kernel_ok(D: int, P: int) -> bool:
+    # head dims and the page size (BBAMD_KV_PAGE_SIZE default) the sparse
+    # kernels cover; any GQA/MQA group width (groups wider than 16 are
+    # chunked in-kernel). Everything else runs the composition.
+    return _SPARSE_KERNEL and D in (64, 128, 256) and P == 16
 
 
 def attn_decode(
@@ -141,6 +171,13 @@ def attn_decode(
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if _attn_sparsity < 1.0 and window <= 0:
+        if _on_gpu(q) and _sparse_kernel_ok(q.shape[-1], k_pages.shape[2]):
+            _require_ext()
+            al = (alibi_slopes.float().to(q.device).contiguous()
+                  if alibi_slopes is not None else None)
+            return hip_ops.attn_decode_sparse(
+                q.contiguous(), k_pages, v_pages, page_table, ctx_lens.int(),
+                _attn_sparsity, scale, al)
         return ref.attn_paged_topk(q, k_pages, v_pages, page_table, ctx_lens,
                                    _attn_sparsity, scale,
                                    alibi_slopes=alibi_slopes)
@@ -224,6 +261,18 @@ def attn_paged_qkv(qkv, Hq: int, Hkv: int, k_pages, v_pages, page_table,
     D = k_pages.shape[3]
     if scale is None:
         scale = 1.0 / math.sqrt(D)
+    if _attn_sparsity < 1.0 and T == 1 and window <= 0:
+        ctx = q_start + 1
+        if (_on_gpu(qkv) and _sparse_kernel_ok(D, k_pages.shape[2])
+                and qkv.is_contiguous()):
+            _require_ext()
+            return hip_ops.attn_decode_sparse_qkv(
+                qkv, Hq, k_pages, v_pages, page_table, ctx.int(),
+                _attn_sparsity, scale)
+        q = qkv[..., : Hq * D].view(B, T, Hq, D).permute(0, 2, 1, 3).contiguous()
+        out = ref.attn_paged_topk(q, k_pages, v_pages, page_table, ctx,
+                                  _attn_sparsity, scale)
+        return out.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
     if _on_gpu(qkv):
         _require_ext()
         if T == 1:
@@ -242,7 +291,9 @@ def attn_paged(q, k_pages, v_pages, page_table, q_start, scale=None, window: int
                tree_mask=None, alibi_slopes=None):
     """Unified entry: picks decode vs prefill kernel by Tq."""
     Tq = q.shape[2]
-    if alibi_slopes is not None and not _on_gpu(q):
+    sparse_decode = (_attn_sparsity < 1.0 and Tq == 1 and tree_mask is None
+                     and window <= 0)
+    if alibi_slopes is not None and not _on_gpu(q) and not sparse_decode:
         if scale is None:
             scale = 1.0 / math.sqrt(q.shape[-1])
         return ref.attn_paged(q, k_pages, v_pages, page_table, q_start, scale,

@@ -341,10 +341,14 @@ def attn_paged_topk(
             scores = scores + alibi_slopes.float().to(q.device).view(-1, 1) * \
                 torch.arange(ctx, dtype=torch.float32, device=q.device)
         kkeep = max(1, min(ctx, math.ceil(sparsity * ctx)))
-        top = scores.topk(kkeep, dim=-1)                        # (Hq, kkeep)
-        w = torch.softmax(top.values, dim=-1)                   # renormalized
+        # prefix of a STABLE descending sort: among scores equal to the
+        # kkeep-th largest the lowest positions win (deterministic; the
+        # device kernel resolves ties the same way)
+        srt = scores.sort(dim=-1, descending=True, stable=True)
+        top_v, top_i = srt.values[:, :kkeep], srt.indices[:, :kkeep]
+        w = torch.softmax(top_v, dim=-1)                        # renormalized
         vsel = torch.gather(
-            vg, 1, top.indices.unsqueeze(-1).expand(-1, -1, D))  # (Hq, kk, D)
+            vg, 1, top_i.unsqueeze(-1).expand(-1, -1, D))       # (Hq, kk, D)
         out[b, :, 0] = torch.einsum("hk,hkd->hd", w, vsel).to(q.dtype)
     return out
 
