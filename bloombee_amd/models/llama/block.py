@@ -81,6 +81,10 @@ class LlamaBlock(torch.nn.Module):
         self._ss_h2 = None
         self._ss_hidden = None
         self._ss_valid = False
+        # split-K tickets of the in-launch combine (ops.linear cnt=...): one
+        # int32 buffer, a slice of H/64 entries each for o-proj and down-proj;
+        # zero between launches (the kernel resets what it counted)
+        self._splitk_cnt = None
 
     @torch.no_grad()
     def init_random(self, seed: Optional[int] = None):
@@ -117,6 +121,8 @@ class LlamaBlock(torch.nn.Module):
             self._ss_h2 = torch.empty(st * 32, dtype=torch.float32,
                                       device=device)
             self._ss_hidden = torch.empty_like(self._ss_h2)
+            self._splitk_cnt = torch.zeros(2 * st, dtype=torch.int32,
+                                           device=device)
 
     @torch.no_grad()
     def fold_norm_weights(self):
@@ -224,12 +230,18 @@ class LlamaBlock(torch.nn.Module):
         if fuse_norm and not getattr(self, "_norm_folded", False):
             self.fold_norm_weights()   # one-time reparameterization
         pb = getattr(self, "prev_block", None)
+        # the qkv GEMM's split-K combine folds into rope_kv_write: the GEMM
+        # hands over its f32 slabs and the combine launch disappears
+        defer = fuse_norm and ops.fuse_qkv_rope_ok(hidden, self.qkv_w, D)
         if fuse_norm and pb is not None and getattr(pb, "_ss_valid", False):
             # previous block's down-proj left sum-of-squares for `hidden`;
             # norm weight is folded into qkv_w -> invr-only norm (mode 2)
             qkv = ops.linear(hidden, self.qkv_w,
                              norm=(None, cfg.rms_norm_eps),
-                             ss_in=pb._ss_hidden)
+                             ss_in=pb._ss_hidden, defer_combine=defer)
+        elif defer:
+            x = ops.rms_norm(hidden, self.input_norm_w, cfg.rms_norm_eps)
+            qkv = ops.linear(x, self.qkv_w, defer_combine=True)
         else:
             x = ops.rms_norm(hidden, self.input_norm_w, cfg.rms_norm_eps)
             qkv = self._lin(x, self.qkv_w, "qkv_w")        # (B, T, (Hq+2Hkv)D)
@@ -247,8 +259,16 @@ class LlamaBlock(torch.nn.Module):
                             .view(1, T)).int()
         # fused RoPE + paged KV write on the raw GEMM output, then attention
         # reads q in place and emits the O-projection input — no transposes
-        ops.rope_kv_write_(qkv, Hq, Hkv, cos, sin, position_ids, kp, vp, pt,
-                           start_pos)
+        ctx_lens = None   # start_pos + T, a by-product of the fused launch
+        if defer and qkv.dtype == torch.float32:
+            # uncombined split-K slabs: combine + RoPE + page write in one
+            # launch; only the q section of the returned buffer is filled
+            qkv, ctx_lens = ops.rope_kv_write_part(
+                qkv, None, B, T, Hq, Hkv, cos, sin, position_ids, kp, vp, pt,
+                start_pos)
+        else:
+            ops.rope_kv_write_(qkv, Hq, Hkv, cos, sin, position_ids, kp, vp,
+                               pt, start_pos)
         hp = (kv.host_prefix(self.layer_index)
               if hasattr(kv, "host_prefix") else None)
         if hp is not None:
@@ -271,20 +291,31 @@ class LlamaBlock(torch.nn.Module):
             attn = attn.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
         else:
             attn = ops.attn_paged_qkv(qkv, Hq, Hkv, kp, vp, pt, start_pos,
-                                      self.scale)
+                                      self.scale,
+                                      ctx_lens=ctx_lens if T == 1 else None)
         if fuse_norm:
             # h2 = hidden + o(attn) via the GEMM's residual epilogue, which
             # also emits row sum-of-squares; the post-attention rmsnorm
             # folds into the gate_up A-stage consuming them. down-proj
             # leaves the stats for the NEXT block's input norm.
             self._ensure_ss_bufs(hidden.device)
+            st = H // 64
             h2 = ops.linear(attn, self.o_w, residual=hidden,
-                            ss_out=self._ss_h2)
-            gu = ops.linear(h2, self.gate_up_w,
-                            norm=(None, cfg.rms_norm_eps),
-                            ss_in=self._ss_h2)
-            out = ops.linear(ops.swiglu(gu), self.down_w, residual=h2,
-                             ss_out=self._ss_hidden)
+                            ss_out=self._ss_h2,
+                            cnt=(self._splitk_cnt[:st]
+                                 if ops.inlaunch_combine_ok(attn, self.o_w, "o")
+                                 else None))
+            # SwiGLU rides the gate_up GEMM's epilogue where available
+            # (ops.linear_swiglu falls back to linear + swiglu, same bits)
+            act = ops.linear_swiglu(h2, self.gate_up_w,
+                                    norm=(None, cfg.rms_norm_eps),
+                                    ss_in=self._ss_h2)
+            out = ops.linear(act, self.down_w, residual=h2,
+                             ss_out=self._ss_hidden,
+                             cnt=(self._splitk_cnt[st:]
+                                  if ops.inlaunch_combine_ok(act, self.down_w,
+                                                             "down")
+                                  else None))
             self._ss_valid = True
             return out
         a = self._lin(attn, self.o_w, "o_w")

@@ -14,12 +14,16 @@ from bloombee_amd.ops.interface import (  # noqa: F401
     attn_paged_qkv,
     attn_prefill,
     fuse_norm_linear_ok,
+    fuse_qkv_rope_ok,
+    fuse_swiglu_ok,
     gelu_tanh,
     hip_ops,
+    inlaunch_combine_ok,
     kv_gather,
     kv_write,
     layer_norm,
     linear,
+    linear_swiglu,
     linear_w4,
     mfma_selftest,
     moe_gemm_grouped,
@@ -29,6 +33,7 @@ from bloombee_amd.ops.interface import (  # noqa: F401
     rms_norm_residual,
     rope_apply_,
     rope_kv_write_,
+    rope_kv_write_part,
     rope_cos_sin,
     set_attn_sparsity,
     swiglu,

@@ -7,6 +7,7 @@
 #define DEVINL __device__ __forceinline__
 
 typedef __attribute__((ext_vector_type(8))) short short8;   // 8 x bf16 = 16 B
+typedef __attribute__((ext_vector_type(4))) short short4v;  // 4 x bf16 = 8 B
 typedef __attribute__((ext_vector_type(4))) float f32x4;    // MFMA 16x16 accum
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 

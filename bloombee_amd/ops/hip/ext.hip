@@ -671,11 +671,67 @@ void rope_kv_write_(torch::Tensor qkv, long Hq_, long Hkv_, torch::Tensor cos_t,
     pos_ptr = pos->data_ptr<int>();
   }
   dim3 grid(B * T, Hq + 2 * Hkv);
-  rope_kv_write_kernel<<<grid, 64, 0, cur_stream()>>>(
-      bf_ptr_mut(qkv), cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), pos_ptr,
+  rope_kv_write_kernel<false><<<grid, 64, 0, cur_stream()>>>(
+      bf_ptr_mut(qkv), nullptr, nullptr, 0, cos_t.data_ptr<float>(),
+      sin_t.data_ptr<float>(), pos_ptr,
       bf_ptr_mut(k_pages), bf_ptr_mut(v_pages), page_table.data_ptr<int>(),
       start_pos.data_ptr<int>(), B, Hq, Hkv, T, D, P, maxp,
       (int)cos_t.size(0));
+}
+
+// The same on the QKV GEMM's uncombined split-K output: part is f32
+// (ksplit, B*T, (Hq+2Hkv)*D) from gemm_skinny(defer_combine=true). Sums the
+// slabs (+bias) as the combine kernel would, ropes, writes K/V to the pages
+// and returns the bf16 (B, T, (Hq+2Hkv)*D) buffer whose q section is filled;
+// its k and v sections are NOT written. Second result: (B,) int32
+// start_pos + T, the context lengths the attention launch takes next.
+std::vector<torch::Tensor> rope_kv_write_part(torch::Tensor part,
+                                 c10::optional<torch::Tensor> bias, long B_,
+                                 long T_, long Hq_, long Hkv_,
+                                 torch::Tensor cos_t, torch::Tensor sin_t,
+                                 c10::optional<torch::Tensor> pos,
+                                 torch::Tensor k_pages, torch::Tensor v_pages,
+                                 torch::Tensor page_table,
+                                 torch::Tensor start_pos) {
+  CHECK_DEV(part); CHECK_CONTIG(part);
+  CHECK_DEV_ALL3(k_pages, page_table, start_pos);
+  CHECK_DEV_ALL3(cos_t, sin_t, v_pages);
+  CHECK_BF16(k_pages); CHECK_CONTIG(k_pages); CHECK_CONTIG(v_pages);
+  if (pos.has_value()) CHECK_DEV((*pos));
+  const int Hq = (int)Hq_, Hkv = (int)Hkv_, B = (int)B_, T = (int)T_;
+  const int P = k_pages.size(2), D = k_pages.size(3);
+  const int maxp = page_table.size(1);
+  const long X = Hq + 2 * Hkv;
+  TORCH_CHECK(part.scalar_type() == at::kFloat && part.dim() == 3 &&
+              part.size(1) == (long)B * T && part.size(2) == X * D,
+              "part must be f32 (ksplit, B*T, (Hq+2Hkv)*D)");
+  TORCH_CHECK(D % 8 == 0, "rope_kv_write_part needs head_dim % 8 == 0");
+  TORCH_CHECK(cos_t.scalar_type() == at::kFloat && cos_t.size(1) == D / 2);
+  TORCH_CHECK(page_table.scalar_type() == at::kInt &&
+              start_pos.scalar_type() == at::kInt &&
+              page_table.size(0) == B && start_pos.numel() == B);
+  const unsigned short* bp = nullptr;
+  if (bias.has_value()) {
+    CHECK_DEV((*bias)); CHECK_BF16((*bias));
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == X * D);
+    bp = bf_ptr(*bias);
+  }
+  const int* pos_ptr = nullptr;
+  if (pos.has_value()) {
+    TORCH_CHECK(pos->scalar_type() == at::kInt && pos->numel() == (long)B * T);
+    pos_ptr = pos->data_ptr<int>();
+  }
+  auto qkv = torch::empty({(long)B, (long)T, X * D},
+                          k_pages.options().dtype(at::kBFloat16));
+  auto ctx = torch::empty({(long)B}, start_pos.options());
+  dim3 grid(B * T, Hq + 2 * Hkv);
+  rope_kv_write_kernel<true><<<grid, 64, 0, cur_stream()>>>(
+      bf_ptr_mut(qkv), part.data_ptr<float>(), bp, (int)part.size(0),
+      cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), pos_ptr,
+      bf_ptr_mut(k_pages), bf_ptr_mut(v_pages), page_table.data_ptr<int>(),
+      start_pos.data_ptr<int>(), B, Hq, Hkv, T, D, P, maxp,
+      (int)cos_t.size(0), ctx.data_ptr<int>());
+  return {qkv, ctx};
 }
 
 
@@ -851,7 +907,15 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
                           c10::optional<torch::Tensor> norm_w, double eps,
                           c10::optional<torch::Tensor> ss_in,
                           c10::optional<torch::Tensor> ss_out,
-                          long norm_mode_req) {
+                          long norm_mode_req, bool defer_combine,
+                          c10::optional<torch::Tensor> cnt) {
+  // defer_combine: under split-K skip the combine and return the f32 slabs
+  // (ksplit, M, N) for a consumer that folds them itself (rope_kv_write_part);
+  // bias is then the consumer's to add. With ksplit == 1 there is nothing to
+  // defer and the finished bf16 C comes back as usual.
+  // cnt: (>= N/64,) int32 zeros — under split-K on the v2 kernel the combine
+  // runs inside the GEMM launch (last-arriver reduction); the kernel leaves
+  // the counters zero again.
   CHECK_DEV(A); CHECK_BF16(A); CHECK_CONTIG(A);
   CHECK_DEV(W); CHECK_BF16(W); CHECK_CONTIG(W);
   const int K = A.size(-1);
@@ -939,6 +1003,26 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
                         torch::TensorOptions().device(A.device()).dtype(at::kFloat));
     pp = part.data_ptr<float>();
   }
+  int* cntp = nullptr;
+  if (cnt.has_value() && ksplit > 1 && v2) {
+    CHECK_DEV((*cnt));
+    TORCH_CHECK(!defer_combine, "cnt and defer_combine exclude each other");
+    TORCH_CHECK(cnt->scalar_type() == at::kInt && cnt->is_contiguous() &&
+                cnt->numel() >= N / 64, "cnt must be int32 of >= N/64 entries");
+    cntp = cnt->data_ptr<int>();
+  }
+  if (cntp) {
+    // combine inside the launch: 1-D grid, tile = id / ksplit after the remap
+    auto launch_r = [&](auto mt) {
+      gemm_skinny_v2_kernel<decltype(mt)::value, 2>
+          <<<dim3((N / 64) * ksplit), 256, 0, cur_stream()>>>(
+              bf_ptr(A), bf_ptr(W), rp, bp, bf_ptr_mut(C), pp, M, N, K, kchunk,
+              ksplit, nwp, (float)eps, norm_mode, ssinp, nstripes, ssoutp, cntp);
+    };
+    if (M <= 16) launch_r(std::integral_constant<int, 1>{});
+    else launch_r(std::integral_constant<int, 2>{});
+    return C;
+  }
   dim3 grid(N / 64, ksplit);
   auto launch = [&](auto mt) {
     if (v2)
@@ -957,6 +1041,10 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
   };
   if (M <= 16) launch(std::integral_constant<int, 1>{});
   else launch(std::integral_constant<int, 2>{});
+  if (ksplit > 1 && defer_combine) {
+    TORCH_CHECK(!rp && !ssoutp, "defer_combine takes no residual / ss_out");
+    return part;
+  }
   if (ksplit > 1) {
     // the vectorized (float4-per-lane) combine serves both the ss-emitting
     // and plain cases; the flat grid-stride combine remains the fallback
@@ -973,6 +1061,51 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
           pp, rp, bp, bf_ptr_mut(C), M, N, ksplit);
     }
   }
+  return C;
+}
+
+// act(M, I) = swiglu(A(M,K) @ W(2I,K)^T), W the fused gate|up weight in its
+// usual layout, M <= 32: the gate_up GEMM with SwiGLU in its epilogue
+// (gemm_skinny_v2_kernel<MT, 1>). norm_mode 0, or 2 (norm weight folded into
+// W, per-row 1/rms from ss_in or from A). Bit-identical to
+// swiglu(gemm_skinny(A, W, ...)).
+torch::Tensor gemm_skinny_swiglu(torch::Tensor A, torch::Tensor W, double eps,
+                                 c10::optional<torch::Tensor> ss_in,
+                                 long norm_mode_req) {
+  CHECK_DEV(A); CHECK_BF16(A); CHECK_CONTIG(A);
+  CHECK_DEV(W); CHECK_BF16(W); CHECK_CONTIG(W);
+  const int K = A.size(-1);
+  const int M = A.numel() / K;
+  const int N = W.size(0);
+  const int I = N / 2;
+  const int norm_mode = (int)norm_mode_req;
+  TORCH_CHECK(M >= 1 && M <= 32, "gemm_skinny_swiglu is for 1 <= M <= 32, got ", M);
+  TORCH_CHECK(W.dim() == 2 && W.size(1) == K, "A/W K mismatch");
+  TORCH_CHECK(N % 2 == 0 && I % 32 == 0 && K % 256 == 0,
+              "gemm_skinny_swiglu needs I % 32 == 0 and K % 256 == 0");
+  TORCH_CHECK(norm_mode == 0 || norm_mode == 2, "norm_mode must be 0 or 2");
+  const float* ssinp = nullptr;
+  int nstripes = 0;
+  if (ss_in.has_value()) {
+    CHECK_DEV((*ss_in));
+    TORCH_CHECK(norm_mode == 2, "ss_in only meaningful with norm_mode 2");
+    TORCH_CHECK(ss_in->is_contiguous() && ss_in->scalar_type() == at::kFloat &&
+                ss_in->numel() % 32 == 0, "ss_in must be f32 (nstripes,32)");
+    ssinp = ss_in->data_ptr<float>();
+    nstripes = (int)(ss_in->numel() / 32);
+  }
+  auto sizes = A.sizes().vec();
+  sizes.back() = I;
+  auto C = torch::empty(sizes, A.options());
+  auto launch = [&](auto mt) {
+    gemm_skinny_v2_kernel<decltype(mt)::value, 1>
+        <<<dim3(I / 32), 256, 0, cur_stream()>>>(
+            bf_ptr(A), bf_ptr(W), nullptr, nullptr, bf_ptr_mut(C), nullptr, M,
+            N, K, K, 1, nullptr, (float)eps, norm_mode, ssinp, nstripes,
+            nullptr, nullptr);
+  };
+  if (M <= 16) launch(std::integral_constant<int, 1>{});
+  else launch(std::integral_constant<int, 2>{});
   return C;
 }
 
@@ -1070,7 +1203,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("residual") = c10::nullopt, py::arg("bias") = c10::nullopt,
         py::arg("ksplit") = 0, py::arg("norm_w") = c10::nullopt,
         py::arg("eps") = 0.0, py::arg("ss_in") = c10::nullopt,
-        py::arg("ss_out") = c10::nullopt, py::arg("norm_mode") = 0);
+        py::arg("ss_out") = c10::nullopt, py::arg("norm_mode") = 0,
+        py::arg("defer_combine") = false, py::arg("cnt") = c10::nullopt);
+  m.def("gemm_skinny_swiglu", &gemm_skinny_swiglu, py::arg("A"), py::arg("W"),
+        py::arg("eps") = 0.0, py::arg("ss_in") = c10::nullopt,
+        py::arg("norm_mode") = 0);
+  m.def("rope_kv_write_part", &rope_kv_write_part);
   m.def("moe_gemm", &moe_gemm);
   m.def("gemm_w4", &gemm_w4);
   m.def("quant4_pack", &quant4_pack);

@@ -104,6 +104,45 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(
   }
 }
 
+// Split-K combine epilogue for one lane: folds the ksplit f32 slabs of row m,
+// columns n0+c4..+3 in split order, then bias, then residual, stores bf16 and
+// (ssout) emits the stripe's row sum-of-squares through a 16-lane butterfly.
+// Shared by gemm_skinny_combine_ss_kernel and the in-launch reducer of
+// gemm_skinny_v2_kernel<MT, 2> so both produce the same bits. The slabs are
+// NOT __restrict__/const: the in-launch reducer reads bytes other workgroups
+// of the same launch wrote, which must stay on the vector-load path.
+DEVINL void gemm_skinny_combine_lane(
+    const float* Cpart, const unsigned short* __restrict__ R,
+    const unsigned short* __restrict__ bias, unsigned short* __restrict__ C,
+    float* __restrict__ ssout, int M, int N, int ksplit, int stripe, int m,
+    int lane) {
+  const int n0 = stripe * 64;
+  const int c4 = (lane & 15) * 4;            // first of this lane's 4 cols
+  const long total = (long)M * N;
+  const long i = (long)m * N + n0 + c4;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < ksplit; ++s) {
+    const f32x4 p = *reinterpret_cast<const f32x4*>(Cpart + s * total + i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] += p[e];
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (bias) v[e] += bf2f(bias[n0 + c4 + e]);
+    if (R) v[e] += bf2f(R[i + e]);
+  }
+  short4v o4;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o4[e] = (short)f2bf(v[e]);
+  *reinterpret_cast<short4v*>(C + i) = o4;
+  if (ssout) {
+    float vs = v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+#pragma unroll
+    for (int msk = 1; msk < 16; msk <<= 1) vs += __shfl_xor(vs, msk);
+    if ((lane & 15) == 0) ssout[(long)stripe * 32 + m] = vs;
+  }
+}
+
 // v2: software-pipelined direct-VGPR W streaming + A through LDS.
 // The guide's verdicts for this shape class (cdna_hip_programming.md):
 //  * "GEMV / M <= 16 decode weights" — W is streamed once and not shared
@@ -116,7 +155,27 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(
 //    to LDS once per stage with full-line loads and A fragments come from
 //    conflict-free padded ds_read_b128.
 // Host guarantees (k1 - k0) % 256 == 0 so the set pairing needs no tail.
-template <int MT>
+//
+// EPI selects the epilogue; the main loop is shared.
+//  0: C / split-K slabs as described above (every caller before the fused
+//     epilogues; its code is what it was).
+//  1: SwiGLU of a fused gate|up weight W (2I, K), N = 2I. The grid is I/32
+//     workgroups of 32 activation columns: in each wave lanes li < 8 stream
+//     gate rows tile*32 + wave*8 + li and lanes li >= 8 the matching up rows
+//     I + tile*32 + wave*8 + (li-8), so the weights keep their gate|up layout
+//     and every lane still streams one W row. The epilogue rounds both values
+//     to bf16 exactly as the plain store would, pairs them with one cross-lane
+//     move (8 lanes apart), applies swiglu_kernel's expression and writes
+//     C (M, I) in full 64 B rows staged through the dead A tile.
+//  2: split-K with the combine inside the launch. The grid is 1-D,
+//     (N/64)*ksplit blocks, tile = id / ksplit, slice = id % ksplit after the
+//     XCD remap (a tile's slices share an XCD when (N/64) % 8 == 0). Every
+//     block stores its slab to Cpart with 16 B stores, releases at agent
+//     scope and draws a ticket from cnt[tile]; the block that draws ksplit-1
+//     acquires, folds all slabs with gemm_skinny_combine_lane (the separate
+//     combine kernel's epilogue, same bits) and resets the counter. Nobody
+//     waits on anybody: no polling, nothing to hang.
+template <int MT, int EPI = 0>
 __global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(
     const unsigned short* __restrict__ A,   // (M, K) bf16
     const unsigned short* __restrict__ W,   // (N, K) bf16
@@ -132,7 +191,8 @@ __global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(
                                //    (zero per-stage cost; the production path)
     const float* __restrict__ ssin,   // (nstripes, 32) producer row sum-sq
     int nstripes,
-    float* __restrict__ ssout) {      // (N/64, 32) this GEMM's row sum-sq
+    float* __restrict__ ssout,        // (N/64, 32) this GEMM's row sum-sq
+    int* cnt = nullptr) {             // EPI 2: (N/64,) tickets, zero on entry
   constexpr int U = 4;                     // k-slices per pipeline set (128 k)
   constexpr int KSTEP = 256;               // A elements staged per stage
   constexpr int RSTRIDE = KSTEP + 8;       // padded LDS row stride (elements)
@@ -162,12 +222,18 @@ __global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(
     if (nwg >= 8)
       tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig8;
   }
+  int split = blockIdx.y;
+  if constexpr (EPI == 2) {
+    split = tile % ksplit;
+    tile /= ksplit;
+  }
   const int n0 = tile * 64 + wave * 16;
-  const int split = blockIdx.y;
   const int k0 = split * kchunk;
   const int k1 = min(K, k0 + kchunk);
 
   const unsigned short* wrow = W + (long)(n0 + li) * K;
+  if constexpr (EPI == 1)
+    wrow = W + ((long)(li < 8 ? 0 : N / 2 - 8) + tile * 32 + wave * 8 + li) * K;
 
   f32x4 acc[MT];
 #pragma unroll
@@ -319,6 +385,90 @@ __global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(
 
   if (norm_mode == 2) reduce_invr();
 
+  if constexpr (EPI == 1) {
+    // C layout per wave: row = t*16 + hi*4 + reg; col li < 8 is gate column
+    // tile*32 + wave*8 + li, col li >= 8 the up value of column li - 8.
+    unsigned short* otile = atile;          // (32 rows, 32 cols) bf16, dead A
+    __syncthreads();                        // every wave is done reading A
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int m = t * 16 + hi * 4 + reg;
+        float v = acc[t][reg];
+        if (norm_mode == 2) v *= invr[m];
+        const float g = bf2f(f2bf(v));      // what the gate_up store rounds to
+        const float u = __shfl_xor(g, 8);   // partner lane's up value
+        const float sg = g / (1.f + fast_expf(-g));
+        if (li < 8) otile[m * 32 + wave * 8 + li] = f2bf(sg * u);
+      }
+    __syncthreads();
+    if (threadIdx.x < 128) {
+      const int m = threadIdx.x >> 2, c8 = (threadIdx.x & 3) * 8;
+      if (m < M)
+        *reinterpret_cast<short8*>(C + (long)m * (N / 2) + tile * 32 + c8) =
+            *reinterpret_cast<const short8*>(otile + m * 32 + c8);
+    }
+    return;
+  }
+
+  if constexpr (EPI == 2) {
+    // Transpose the accumulators through the dead A tile so the slab goes
+    // out row-major in the combine's lane mapping: one 16 B store per lane.
+    constexpr int TS = 68;                  // padded f32 row stride
+    float* ftile = reinterpret_cast<float*>(atile);   // (32, TS) f32
+    __syncthreads();                        // every wave is done reading A
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int m = t * 16 + hi * 4 + reg;
+        float v = acc[t][reg];
+        if (norm_mode == 2) v *= invr[m];
+        ftile[m * TS + wave * 16 + li] = v;
+      }
+    __syncthreads();
+    float* dst = Cpart + (long)split * M * N;
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      const int m = t * 16 + wave * 4 + hi;
+      if (m < M)
+        *reinterpret_cast<f32x4*>(dst + (long)m * N + tile * 64 + li * 4) =
+            *reinterpret_cast<const f32x4*>(ftile + m * TS + li * 4);
+    }
+    // publish: every storing wave drains, then ONE lane releases at agent
+    // scope and draws the ticket (fence before the add, wait in between)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    int* flag = reinterpret_cast<int*>(ssp);   // "I am last", existing LDS
+    if (threadIdx.x == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const int ticket = __hip_atomic_fetch_add(
+          cnt + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int last = ticket == ksplit - 1;
+      if (last) {
+        // all ksplit tickets of this tile are drawn: leave the counter
+        // zero for the next launch (graph replays start clean)
+        __hip_atomic_store(cnt + tile, 0, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      flag[0] = last;
+    }
+    __syncthreads();
+    if (!flag[0]) return;
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      const int m = t * 16 + wave * 4 + hi;
+      if (m < M)
+        gemm_skinny_combine_lane(Cpart, R, bias, C, ssout, M, N, ksplit, tile,
+                                 m, lane);
+    }
+    return;
+  }
+
   if (ksplit == 1) {
     if (ssout == nullptr) {
 #pragma unroll
@@ -387,34 +537,11 @@ __global__ __launch_bounds__(256) void gemm_skinny_combine_ss_kernel(
     const float* __restrict__ Cpart, const unsigned short* __restrict__ R,
     const unsigned short* __restrict__ bias, unsigned short* __restrict__ C,
     float* __restrict__ ssout, int M, int N, int ksplit) {
-  const int n0 = blockIdx.x * 64;
   const int lane = threadIdx.x & (WAVE - 1);
-  const int c4 = (lane & 15) * 4;            // first of this lane's 4 cols
   const int m = blockIdx.y * 16 + (threadIdx.x >> 6) * 4 + (lane >> 4);
   if (m >= M) return;
-  const long total = (long)M * N;
-  const long i = (long)m * N + n0 + c4;
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  for (int s = 0; s < ksplit; ++s) {
-    const f32x4 p = *reinterpret_cast<const f32x4*>(Cpart + s * total + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] += p[e];
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    if (bias) v[e] += bf2f(bias[n0 + c4 + e]);
-    if (R) v[e] += bf2f(R[i + e]);
-  }
-  short4v o4;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o4[e] = (short)f2bf(v[e]);
-  *reinterpret_cast<short4v*>(C + i) = o4;
-  if (ssout) {
-    float vs = v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-#pragma unroll
-    for (int msk = 1; msk < 16; msk <<= 1) vs += __shfl_xor(vs, msk);
-    if ((lane & 15) == 0) ssout[(long)blockIdx.x * 32 + m] = vs;
-  }
+  gemm_skinny_combine_lane(Cpart, R, bias, C, ssout, M, N, ksplit, blockIdx.x,
+                           m, lane);
 }
 
 __global__ void gemm_skinny_combine_kernel(

@@ -249,12 +249,32 @@ def rope_kv_write_(qkv, Hq: int, Hkv: int, cos, sin, position_ids,
     ref.kv_write(k2, v.contiguous(), k_pages, v_pages, page_table, start_pos)
 
 
+def rope_kv_write_part(part, bias, B: int, T: int, Hq: int, Hkv: int, cos, sin,
+                       position_ids, k_pages, v_pages, page_table, start_pos):
+    """rope_kv_write_ on the QKV GEMM's uncombined split-K output.
+
+    part: f32 (ksplit, B*T, (Hq+2Hkv)*D) from linear(defer_combine=True); the
+    kernel sums the slabs in split order (+bias), rounds once to bf16 — the
+    value the combine kernel would have stored — and ropes / page-writes it.
+    Returns the bf16 (B, T, (Hq+2Hkv)*D) buffer with the q section roped —
+    its k and v sections are NOT written (they live in the pages only) — and
+    the (B,) int32 context lengths start_pos + T, which attn_paged_qkv takes
+    as ctx_lens at T == 1 instead of launching its own start_pos + 1."""
+    _require_ext()
+    return hip_ops.rope_kv_write_part(
+        part, bias, B, T, Hq, Hkv, cos, sin,
+        position_ids.int() if position_ids is not None else None,
+        k_pages, v_pages, page_table, start_pos.int())
+
+
 def attn_paged_qkv(qkv, Hq: int, Hkv: int, k_pages, v_pages, page_table,
-                   q_start, scale=None, window: int = 0):
+                   q_start, scale=None, window: int = 0, ctx_lens=None):
     """Attention reading q straight from the fused QKV buffer.
 
     qkv: (B, T, (Hq+2Hkv)*D) with the q section already roped and the new
     tokens' K/V already in the pages (rope_kv_write_ first).
+    ctx_lens: optional precomputed q_start + 1 for single-token decode
+    (rope_kv_write_part's second result).
     Returns (B, T, Hq*D) — the O-projection GEMM input, no transposes.
     """
     B, T, _ = qkv.shape
@@ -262,7 +282,7 @@ def attn_paged_qkv(qkv, Hq: int, Hkv: int, k_pages, v_pages, page_table,
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     if _attn_sparsity < 1.0 and T == 1 and window <= 0:
-        ctx = q_start + 1
+        ctx = ctx_lens if ctx_lens is not None else q_start + 1
         if (_on_gpu(qkv) and _sparse_kernel_ok(D, k_pages.shape[2])
                 and qkv.is_contiguous()):
             _require_ext()
@@ -276,7 +296,7 @@ def attn_paged_qkv(qkv, Hq: int, Hkv: int, k_pages, v_pages, page_table,
     if _on_gpu(qkv):
         _require_ext()
         if T == 1:
-            ctx = q_start + 1
+            ctx = ctx_lens if ctx_lens is not None else q_start + 1
             return hip_ops.attn_decode_qkv(qkv, Hq, k_pages, v_pages, page_table,
                                            ctx.int(), scale, window, 0)
         return hip_ops.attn_prefill_qkv(qkv, Hq, k_pages, v_pages, page_table,
@@ -328,7 +348,9 @@ def linear(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = 
            bias: Optional[torch.Tensor] = None,
            norm: Optional[tuple] = None,
            ss_in: Optional[torch.Tensor] = None,
-           ss_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+           ss_out: Optional[torch.Tensor] = None,
+           defer_combine: bool = False,
+           cnt: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = (rmsnorm(x) if norm else x) @ w^T (+bias) (+residual).
     Decode-shaped GEMMs (<=32 rows) on GPU go through the skinny-M MFMA
     kernel (gemm_skinny.hip) — hipBLASLt leaves ~2x weight-stream bandwidth
@@ -338,7 +360,12 @@ def linear(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = 
     read/write disappear from the decode step). ss_in is the producing
     GEMM's per-stripe row sum-of-squares (its ss_out) so the fused norm
     skips re-streaming A; ss_out asks this GEMM's epilogue to emit the
-    same stats for ITS consumer (f32 (N/64, 32), overwritten — graph-safe)."""
+    same stats for ITS consumer (f32 (N/64, 32), overwritten — graph-safe).
+    defer_combine (callers gate on fuse_qkv_rope_ok): where the kernel splits
+    K, return its f32 slabs (ksplit, M, N) WITHOUT bias instead of y, for
+    rope_kv_write_part to fold; an unsplit GEMM still returns y (bf16).
+    cnt (callers gate on inlaunch_combine_ok): int32 zeros, >= N/64 entries —
+    a split-K GEMM combines inside its own launch and leaves them zero."""
     M = x.numel() // x.shape[-1]
     N, K = w.shape[0], x.shape[-1]
     # All decode-shaped GEMMs route to the skinny kernel: although hipBLASLt
@@ -361,9 +388,19 @@ def linear(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = 
                 else:
                     nw = norm[0].contiguous()
                     mode = 1
-            return hip_ops.gemm_skinny(x.contiguous(), w, residual, bias, 0,
-                                       nw, eps, ss_in, ss_out, mode)
+            return hip_ops.gemm_skinny(x.contiguous(), w, residual, bias,
+                                       _INLAUNCH_KSPLIT if cnt is not None else 0,
+                                       nw, eps, ss_in, ss_out, mode,
+                                       defer_combine, cnt)
+        if defer_combine or cnt is not None:
+            return hip_ops.gemm_skinny(x.contiguous(), w, residual, bias,
+                                       _INLAUNCH_KSPLIT if cnt is not None else 0,
+                                       None, 0.0, None, None, 0,
+                                       defer_combine, cnt)
         return hip_ops.gemm_skinny(x.contiguous(), w, residual, bias, 0)
+    if defer_combine or cnt is not None:
+        raise RuntimeError("defer_combine / cnt require the GPU skinny-GEMM "
+                           "path (callers gate on fuse_norm_linear_ok)")
     if norm is not None:
         nw = norm[0]
         if nw is None:
@@ -393,6 +430,84 @@ def fuse_norm_linear_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
     return (_FUSE_NORM and _on_gpu(x) and x.numel() // K <= 32
             and x.dtype == torch.bfloat16 and K % 256 == 0
             and w.shape[0] % 64 == 0 and HAVE_HIP_OPS)
+
+
+# Fused epilogues of the decode GEMMs (profiles/r03_fused_epilogues.md). Each
+# is available only where fuse_norm_linear_ok holds (the llama block's
+# _fuse_norm_gate); =0 restores the separate kernels exactly, and the results
+# are bit-identical either way.
+#   BBAMD_FUSE_SWIGLU    SwiGLU in the gate_up GEMM's epilogue (linear_swiglu)
+#   BBAMD_FUSE_QKV_ROPE  qkv split-K combine folded into rope_kv_write
+#   BBAMD_INLAUNCH_COMBINE  o-proj / down-proj split-K combine inside the GEMM
+#                        launch: "0" none, "1" both, or a list of "o", "down"
+_FUSE_SWIGLU = os.environ.get("BBAMD_FUSE_SWIGLU", "1") != "0"
+_FUSE_QKV_ROPE = os.environ.get("BBAMD_FUSE_QKV_ROPE", "1") != "0"
+_INLAUNCH_DEFAULT = "0"
+
+
+def _parse_inlaunch(v: str) -> frozenset:
+    if v in ("", "0"):
+        return frozenset()
+    if v == "1":
+        return frozenset(("o", "down"))
+    return frozenset(x.strip() for x in v.split(",")) & {"o", "down"}
+
+
+_INLAUNCH_COMBINE = _parse_inlaunch(
+    os.environ.get("BBAMD_INLAUNCH_COMBINE", _INLAUNCH_DEFAULT))
+# experiment knob for the in-launch ksplit sweep; 0 = the op's own rule
+_INLAUNCH_KSPLIT = int(os.environ.get("BBAMD_INLAUNCH_KSPLIT", "0"))
+
+
+def fuse_swiglu_ok(x: torch.Tensor, gate_up_w: torch.Tensor) -> bool:
+    """True when linear_swiglu(x, gate_up_w) runs the fused kernel: the
+    fuse_norm_linear_ok shapes, and only where the plain gate_up GEMM would
+    not split K. The fused kernel never splits (one f32 accumulator per
+    output), so against a split-K gate_up its sums would be ordered
+    differently and a few outputs would move by a bf16 ulp; such shapes
+    (narrow 2I with K >= 1024) keep the separate kernels."""
+    N, K = gate_up_w.shape[0], x.shape[-1]
+    return (_FUSE_SWIGLU and fuse_norm_linear_ok(x, gate_up_w)
+            and _skinny_auto_ksplit(N, K) == 1)
+
+
+def _skinny_auto_ksplit(N: int, K: int) -> int:
+    """ksplit gemm_skinny picks for itself (ext.hip, ksplit_req == 0)."""
+    if N // 64 >= 256:
+        ks = int(os.environ.get("BBAMD_GEMM_KSPLIT_BIG", "1") or 1)
+    else:
+        ks = min(K // 512, max(1, min(8, 1024 // (N // 64))))
+    return max(1, ks)
+
+
+def fuse_qkv_rope_ok(x: torch.Tensor, qkv_w: torch.Tensor, D: int) -> bool:
+    """True when the qkv GEMM may defer its combine to rope_kv_write_part."""
+    return (_FUSE_QKV_ROPE and fuse_norm_linear_ok(x, qkv_w) and D % 8 == 0)
+
+
+def inlaunch_combine_ok(x: torch.Tensor, w: torch.Tensor, which: str) -> bool:
+    """True when linear(cnt=...) may combine split-K inside the launch for
+    the projection named `which` ("o" or "down")."""
+    return which in _INLAUNCH_COMBINE and fuse_norm_linear_ok(x, w)
+
+
+def linear_swiglu(x: torch.Tensor, gate_up_w: torch.Tensor,
+                  norm: Optional[tuple] = None,
+                  ss_in: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act = swiglu((rmsnorm(x) if norm else x) @ gate_up_w^T), gate_up_w the
+    fused gate|up weight (2I, K) in its usual layout. Decode shapes on GPU
+    run the gate_up GEMM with SwiGLU in its epilogue (one launch, the (M, 2I)
+    intermediate never reaches memory); bit-identical to swiglu(linear(...)).
+    norm is (None, eps): the weight is pre-folded into gate_up_w."""
+    if fuse_swiglu_ok(x, gate_up_w):
+        _require_ext()
+        assert norm is None or norm[0] is None, \
+            "linear_swiglu takes the folded-weight norm only"
+        return hip_ops.gemm_skinny_swiglu(
+            x.contiguous(), gate_up_w,
+            float(norm[1]) if norm is not None else 0.0, ss_in,
+            2 if norm is not None else 0)
+    return swiglu(linear(x, gate_up_w, norm=norm, ss_in=ss_in))
 
 
 # mixed-device decode on the GPU: device segment on the MFMA decode kernel
