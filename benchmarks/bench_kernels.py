@@ -3,7 +3,7 @@
 Reports per-kernel time and effective HBM bandwidth / TFLOPs so kernel
 changes can be A/B'd without the end-to-end bench's noise.
 
-    python benchmarks/bench_kernels.py [attn_decode attn_mixed attn_prefill ...]
+    python benchmarks/bench_kernels.py [attn_decode attn_mixed attn_prefill train_attn ...]
 """
 import math
 import os
@@ -258,11 +258,83 @@ def bench_gemm_norm():
 
 
 
+def _event_time(fn, iters, warmup):
+    """Median of `iters` device-event timings of fn (seconds)."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e-3)
+    ts.sort()
+    return ts[len(ts) // 2]
+
+
+def bench_train_attn():
+    """fwd+bwd of ops.attn_train: the gfx950 kernels against the torch
+    composition on the same GPU, llama-3-8b head geometry, B*T = 4096 tokens.
+    Three alternating rounds per shape (median and spread), plus the peak
+    memory each path adds on top of its inputs. FLOPs are the causal-half
+    counts: forward 2 products, dQ kernel 3, dK/dV kernel 4."""
+    Hq, Hkv, D = 32, 8, 128
+    scale = 1.0 / math.sqrt(D)
+
+    def run(q, k, v, do):
+        out = ops.attn_train(q, k, v, scale)
+        return torch.autograd.grad(out, (q, k, v), do)
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        r = fn()
+        torch.cuda.synchronize()
+        del r
+        return torch.cuda.max_memory_allocated() - base
+
+    for T in (512, 1024, 2048, 4096):
+        B = 4096 // T
+        gen = torch.Generator(device=DEV).manual_seed(T)
+        mk = lambda h: torch.randn(B, T, h, D, generator=gen, device=DEV,
+                                   dtype=torch.bfloat16).requires_grad_(True)
+        q, k, v = mk(Hq), mk(Hkv), mk(Hkv)
+        do = torch.randn(B, T, Hq, D, generator=gen, device=DEV, dtype=torch.bfloat16)
+        pair = B * Hq * D * 2.0 * (T * (T + 1) / 2)     # one causal product
+        times = {"kernel": [], "eager": []}
+        mem = {}
+        for _ in range(3):
+            for path, sw in (("kernel", "1"), ("eager", "0")):
+                os.environ["BBAMD_TRAIN_ATTN_KERNEL"] = sw
+                times[path].append(_event_time(lambda: run(q, k, v, do), 10, 3))
+                mem[path] = peak(lambda: run(q, k, v, do))
+        os.environ.pop("BBAMD_TRAIN_ATTN_KERNEL", None)
+        with torch.no_grad():
+            out, lse = ops.hip_ops.attn_train_fwd(q, k, v, scale, 0, None, True)
+            t_f = _event_time(lambda: ops.hip_ops.attn_train_fwd(
+                q, k, v, scale, 0, None, True), 20, 3)
+            t_b = _event_time(lambda: ops.hip_ops.attn_train_bwd(
+                do, q, k, v, out, lse, scale, 0, None), 20, 3)
+        tk, te = sorted(times["kernel"]), sorted(times["eager"])
+        print(f"train_attn B{B} T{T} Hq{Hq}/{Hkv} D{D}: "
+              f"kernel {tk[1]*1e3:8.3f} ms [{tk[0]*1e3:.3f}..{tk[2]*1e3:.3f}]  "
+              f"eager {te[1]*1e3:8.3f} ms [{te[0]*1e3:.3f}..{te[2]*1e3:.3f}]  "
+              f"eager/kernel {te[1]/tk[1]:5.2f}  "
+              f"peak +{mem['kernel']/2**20:8.1f} MiB vs +{mem['eager']/2**20:8.1f} MiB")
+        print(f"    fwd {t_f*1e3:7.3f} ms {2*pair/t_f/1e12:6.1f} TF/s   "
+              f"bwd (dQ + dK/dV) {t_b*1e3:7.3f} ms {7*pair/t_b/1e12:6.1f} TF/s")
+
+
 ALL = {
     "attn_decode": bench_attn_decode,
     "attn_mixed": bench_attn_mixed,
     "attn_sparse": bench_attn_sparse,
     "attn_prefill": bench_attn_prefill,
+    "train_attn": bench_train_attn,
     "kv_stream": bench_kv_stream,
     "norms": bench_norms,
     "swiglu": bench_swiglu,

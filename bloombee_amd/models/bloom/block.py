@@ -115,15 +115,10 @@ class BloomBlock(torch.nn.Module):
         qkv = torch.nn.functional.linear(x, self.qkv_w, self.qkv_b)
         q, k, v = (t.view(B, T, Hq, D).permute(0, 2, 1, 3)
                    for t in qkv.split(Hq * D, dim=-1))
-        scores = torch.matmul(q.float(), k.float().transpose(-1, -2)) * self.scale
-        pos = torch.arange(start_pos, start_pos + T)
-        scores = scores + self.alibi.view(1, Hq, 1, 1) * \
-            (start_pos + torch.arange(T, dtype=torch.float32)).view(1, 1, 1, T)
-        mask = torch.ones(T, T, dtype=torch.bool).tril()
-        scores = scores.masked_fill(~mask.to(scores.device), float("-inf"))
-        p = torch.softmax(scores, dim=-1)
-        attn = torch.matmul(p, v.float()).to(hidden.dtype)
-        attn = attn.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
+        attn = ops.attn_train(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3),
+                              v.permute(0, 2, 1, 3), self.scale,
+                              alibi_slopes=self.alibi)
+        attn = attn.reshape(B, T, Hq * D)
         h = hidden + torch.nn.functional.linear(attn, self.dense_w, self.dense_b)
         y = ln(h, self.ln2_w, self.ln2_b)
         u = torch.nn.functional.linear(y, self.up_w, self.up_b)

@@ -100,7 +100,6 @@ class FalconBlock(torch.nn.Module):
         B, T, H = hidden.shape
         Hq, Hkv, D = self.Hq, self.Hkv, self.D
         cfg = self.config
-        G = Hq // Hkv
         x = torch.nn.functional.layer_norm(
             hidden.float(), (H,), self.ln_w.float(), self.ln_b.float(),
             cfg.layer_norm_epsilon).to(hidden.dtype)
@@ -109,17 +108,13 @@ class FalconBlock(torch.nn.Module):
         k = qkv[..., Hq * D:(Hq + Hkv) * D].view(B, T, Hkv, D).permute(0, 2, 1, 3)
         v = qkv[..., (Hq + Hkv) * D:].view(B, T, Hkv, D).permute(0, 2, 1, 3)
         cos, sin = self.rope.get(hidden.device)
-        pos = torch.arange(start_pos, start_pos + T).view(1, T).expand(B, T)
+        pos = torch.arange(start_pos, start_pos + T,
+                           device=hidden.device).view(1, T).expand(B, T)
         from bloombee_amd.ops import reference as refops
         q, k = refops.rope_apply(q, k, cos, sin, pos)
-        k = k.repeat_interleave(G, dim=1)
-        v = v.repeat_interleave(G, dim=1)
-        scores = torch.matmul(q.float(), k.float().transpose(-1, -2)) * self.scale
-        mask = torch.ones(T, T, dtype=torch.bool).tril()
-        scores = scores.masked_fill(~mask.to(scores.device), float("-inf"))
-        p = torch.softmax(scores, dim=-1)
-        attn = torch.matmul(p, v.float()).to(hidden.dtype)
-        attn = attn.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
+        attn = ops.attn_train(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3),
+                              v.permute(0, 2, 1, 3), self.scale)
+        attn = attn.reshape(B, T, Hq * D)
         a = torch.nn.functional.linear(attn, self.o_w)
         u = torch.nn.functional.linear(x, self.up_w)
         g = torch.nn.functional.gelu(u.float(), approximate="tanh").to(u.dtype)

@@ -12,6 +12,7 @@ import torch
 from bloombee_amd import ops
 from bloombee_amd.kv.paged import SessionHandle
 from bloombee_amd.models.gemma4.config import Gemma4Config
+from bloombee_amd.ops import reference as refops
 from bloombee_amd.ops.reference import rope_cos_sin
 
 
@@ -198,9 +199,12 @@ class Gemma4Block(torch.nn.Module):
         cos, sin = self._tables(hidden.device)
         pos = torch.arange(start_pos, start_pos + T,
                            device=hidden.device).view(1, T).expand(B, T)
-        G = Hq // Hkv
 
-        x = _rms1p(hidden, self.input_norm_w, eps)
+        def rms(t, w, eps_):
+            # the torch definition: the device rms_norm kernel has no backward
+            return refops.rms_norm(t, w, eps_)
+
+        x = rms(hidden, self.input_norm_w, eps)
         q = torch.nn.functional.linear(x, self.q_w).view(B, T, Hq, D).permute(0, 2, 1, 3)
         q = _rms1p_headdim(q, self.q_norm_w, eps)
         q = _rope_partial(q, cos, sin, pos, self.rot_dim)
@@ -211,27 +215,19 @@ class Gemma4Block(torch.nn.Module):
                 .view(B, T, Hkv, D).permute(0, 2, 1, 3)
                 if self.v_w is not None else kraw)
         v = _rms1p_headdim(vraw, None, eps)
-        k = k.repeat_interleave(G, dim=1)
-        v = v.repeat_interleave(G, dim=1)
-        scores = torch.matmul(q.float(), k.float().transpose(-1, -2))  # scale 1.0
-        qpos = torch.arange(start_pos, start_pos + T).view(T, 1)
-        kpos = torch.arange(start_pos, start_pos + T).view(1, T)
-        mask = kpos <= qpos
-        if self.window > 0:
-            mask &= kpos > qpos - self.window
-        scores = scores.masked_fill(~mask.to(scores.device), float("-inf"))
-        p = torch.softmax(scores, dim=-1)
-        attn = torch.matmul(p, v.float()).to(hidden.dtype)
-        attn = attn.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
+        attn = ops.attn_train(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3),
+                              v.permute(0, 2, 1, 3), 1.0,
+                              window=self.window)
+        attn = attn.reshape(B, T, Hq * D)
         a = torch.nn.functional.linear(attn, self.o_w)
-        a = _rms1p(a, self.post_attn_norm_w, eps)
+        a = rms(a, self.post_attn_norm_w, eps)
         h = hidden + a
-        y = _rms1p(h, self.pre_ffn_norm_w, eps)
+        y = rms(h, self.pre_ffn_norm_w, eps)
         gu = torch.nn.functional.linear(y, self.gate_up_w)
         g, u = gu.split([self.I, self.I], dim=-1)
         gact = torch.nn.functional.gelu(g.float(), approximate="tanh").to(u.dtype)
         m = torch.nn.functional.linear(gact * u, self.down_w)
-        m = _rms1p(m, self.post_ffn_norm_w, eps)
+        m = rms(m, self.post_ffn_norm_w, eps)
         return h + m
 
     def forward(self, *args, **kw):

@@ -333,7 +333,6 @@ class LlamaBlock(torch.nn.Module):
         B, T, H = hidden.shape
         Hq, Hkv, D = self.Hq, self.Hkv, self.D
         cfg = self.config
-        G = Hq // Hkv
 
         def rms(x, w):
             xf = x.float()
@@ -365,14 +364,9 @@ class LlamaBlock(torch.nn.Module):
             return torch.cat([t1 * c - t2 * s, t2 * c + t1 * s], -1).to(t.dtype)
 
         q, k = rot(q), rot(k)
-        k = k.repeat_interleave(G, dim=1)
-        v = v.repeat_interleave(G, dim=1)
-        scores = torch.matmul(q.float(), k.float().transpose(-1, -2)) * self.scale
-        mask = torch.ones(T, T, dtype=torch.bool, device=hidden.device).tril()
-        scores = scores.masked_fill(~mask, float("-inf"))
-        p = torch.softmax(scores, dim=-1)
-        attn = torch.matmul(p, v.float()).to(hidden.dtype)
-        attn = attn.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
+        attn = ops.attn_train(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3),
+                              v.permute(0, 2, 1, 3), self.scale)
+        attn = attn.reshape(B, T, Hq * D)
         h2 = hidden + lin(attn, self.o_w, "o_w")
         y = rms(h2, self.post_norm_w)
         gu = F.linear(y, self.gate_up_w)

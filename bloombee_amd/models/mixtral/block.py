@@ -153,7 +153,6 @@ class MixtralBlock(torch.nn.Module):
         B, T, H = hidden.shape
         Hq, Hkv, D = self.Hq, self.Hkv, self.D
         cfg = self.config
-        G = Hq // Hkv
 
         def rms(x, w):
             xf = x.float()
@@ -165,17 +164,13 @@ class MixtralBlock(torch.nn.Module):
         qkv = qkv.view(B, T, Hq + 2 * Hkv, D).permute(0, 2, 1, 3)
         q, k, v = qkv.split([Hq, Hkv, Hkv], dim=1)
         cos, sin = self.rope.get(hidden.device)
-        pos = torch.arange(start_pos, start_pos + T).view(1, T).expand(B, T)
+        pos = torch.arange(start_pos, start_pos + T,
+                           device=hidden.device).view(1, T).expand(B, T)
         from bloombee_amd.ops import reference as refops
         q, k = refops.rope_apply(q, k, cos, sin, pos)
-        k = k.repeat_interleave(G, dim=1)
-        v = v.repeat_interleave(G, dim=1)
-        scores = torch.matmul(q.float(), k.float().transpose(-1, -2)) * self.scale
-        mask = torch.ones(T, T, dtype=torch.bool).tril()
-        scores = scores.masked_fill(~mask.to(scores.device), float("-inf"))
-        p = torch.softmax(scores, dim=-1)
-        attn = torch.matmul(p, v.float()).to(hidden.dtype)
-        attn = attn.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
+        attn = ops.attn_train(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3),
+                              v.permute(0, 2, 1, 3), self.scale)
+        attn = attn.reshape(B, T, Hq * D)
         h2 = hidden + torch.nn.functional.linear(attn, self.o_w)
         y = rms(h2, self.post_norm_w)
 

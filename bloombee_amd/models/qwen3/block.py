@@ -100,7 +100,6 @@ class Qwen3Block(LlamaBlock):
         B, T, H = hidden.shape
         Hq, Hkv, D = self.Hq, self.Hkv, self.D
         cfg = self.config
-        G = Hq // Hkv
 
         def rms(x, w):
             xf = x.float()
@@ -114,17 +113,13 @@ class Qwen3Block(LlamaBlock):
         q = rms(q, self.q_norm_w)
         k = rms(k, self.k_norm_w)
         cos, sin = self.rope.get(hidden.device)
-        pos = torch.arange(start_pos, start_pos + T).view(1, T).expand(B, T)
+        pos = torch.arange(start_pos, start_pos + T,
+                           device=hidden.device).view(1, T).expand(B, T)
         from bloombee_amd.ops import reference as refops
         q, k = refops.rope_apply(q, k, cos, sin, pos)
-        k = k.repeat_interleave(G, dim=1)
-        v = v.repeat_interleave(G, dim=1)
-        scores = torch.matmul(q.float(), k.float().transpose(-1, -2)) * self.scale
-        mask = torch.ones(T, T, dtype=torch.bool).tril()
-        scores = scores.masked_fill(~mask.to(scores.device), float("-inf"))
-        p = torch.softmax(scores, dim=-1)
-        attn = torch.matmul(p, v.float()).to(hidden.dtype)
-        attn = attn.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
+        attn = ops.attn_train(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3),
+                              v.permute(0, 2, 1, 3), self.scale)
+        attn = attn.reshape(B, T, Hq * D)
         h2 = hidden + torch.nn.functional.linear(attn, self.o_w)
         y = rms(h2, self.post_norm_w)
         gu = torch.nn.functional.linear(y, self.gate_up_w)

@@ -13,6 +13,7 @@ from bloombee_amd.ops.interface import (  # noqa: F401
     attn_paged_mixed_qkv,
     attn_paged_qkv,
     attn_prefill,
+    attn_train,
     fuse_norm_linear_ok,
     fuse_qkv_rope_ok,
     fuse_swiglu_ok,

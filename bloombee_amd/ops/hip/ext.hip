@@ -17,6 +17,7 @@
 #include "attn_decode_mfma.hip"
 #include "attn_sparse.hip"
 #include "attn_prefill.hip"
+#include "attn_train.hip"
 #include "gemm_skinny.hip"
 #include "moe_gemm.hip"
 #include "w4_gemm.hip"
@@ -651,6 +652,130 @@ torch::Tensor attn_prefill_qkv(torch::Tensor qkv, long Hq_,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// training attention (dense K/V, LSE out, flash backward)
+// ---------------------------------------------------------------------------
+
+// (B, T, H, D) bf16 view with a contiguous last dim and 16-byte aligned rows.
+static void check_train_operand(const torch::Tensor& t, const char* name,
+                                long B, long T, long D) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on device");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
+  TORCH_CHECK(t.dim() == 4 && t.size(0) == B && t.size(1) == T && t.size(3) == D,
+              name, " must be (B, T, H, D) matching q");
+  TORCH_CHECK(t.stride(3) == 1, name, " needs a contiguous last dim");
+  TORCH_CHECK(t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
+              t.stride(2) % 8 == 0 && t.storage_offset() % 8 == 0,
+              name, " rows must be 16-byte aligned");
+}
+
+static const float* train_alibi_ptr(const c10::optional<torch::Tensor>& alibi,
+                                    const torch::Tensor& q, long Hq) {
+  if (!alibi.has_value()) return nullptr;
+  TORCH_CHECK(alibi->is_cuda() && alibi->get_device() == q.get_device(),
+              "alibi must be on q's device");
+  TORCH_CHECK(alibi->scalar_type() == at::kFloat && alibi->is_contiguous() &&
+              alibi->numel() == Hq, "alibi must be contiguous f32 (Hq,)");
+  return alibi->data_ptr<float>();
+}
+
+static void check_train_geometry(const torch::Tensor& q, const torch::Tensor& k,
+                                 const torch::Tensor& v, long window) {
+  TORCH_CHECK(q.dim() == 4, "attn_train expects q (B, T, Hq, D)");
+  const long B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
+  TORCH_CHECK(D == 64 || D == 128, "attn_train supports head_dim 64 and 128, got ", D);
+  TORCH_CHECK(B > 0 && T > 0 && Hq > 0, "attn_train: empty input");
+  check_train_operand(q, "q", B, T, D);
+  check_train_operand(k, "k", B, T, D);
+  check_train_operand(v, "v", B, T, D);
+  const long Hkv = k.size(2);
+  TORCH_CHECK(Hkv > 0 && v.size(2) == Hkv && Hq % Hkv == 0,
+              "attn_train: Hq must be a multiple of Hkv, and k/v must agree");
+  TORCH_CHECK(k.get_device() == q.get_device() && v.get_device() == q.get_device(),
+              "attn_train: q, k, v must share a device");
+  TORCH_CHECK(window >= 0 && window < (1L << 30), "attn_train: bad window");
+  const long ntile = (T + TR_ROWS - 1) / TR_ROWS;
+  TORCH_CHECK(T < (1L << 30) && B * Hq * ntile < (1L << 31),
+              "attn_train: grid too large");
+}
+
+std::tuple<torch::Tensor, torch::Tensor> attn_train_fwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, double scale,
+    long window, c10::optional<torch::Tensor> alibi, bool want_lse) {
+  check_train_geometry(q, k, v, window);
+  const long B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
+  const long Hkv = k.size(2);
+  const float* alibi_ptr = train_alibi_ptr(alibi, q, Hq);
+  c10::DeviceGuard guard(q.device());
+  auto out = torch::empty({B, T, Hq, D}, q.options());
+  auto lse = torch::empty({want_lse ? B : 0, Hq, T},
+                          q.options().dtype(at::kFloat));
+  const int ntile = (int)((T + TR_ROWS - 1) / TR_ROWS);
+  const unsigned grid = (unsigned)(B * Hq * ntile);
+  auto launch = [&](auto d) {
+    attn_train_fwd_kernel<decltype(d)::value><<<grid, 512, 0, cur_stream()>>>(
+        bf_ptr(q), bf_ptr(k), bf_ptr(v), alibi_ptr, bf_ptr_mut(out),
+        want_lse ? lse.data_ptr<float>() : nullptr,
+        (int)Hq, (int)(Hq / Hkv), (int)T, ntile, (int)window, (float)scale,
+        q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
+        k.stride(2), v.stride(0), v.stride(1), v.stride(2));
+  };
+  if (D == 128) launch(std::integral_constant<int, 128>{});
+  else launch(std::integral_constant<int, 64>{});
+  return {out, lse};
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> attn_train_bwd(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor out, torch::Tensor lse, double scale, long window,
+    c10::optional<torch::Tensor> alibi) {
+  check_train_geometry(q, k, v, window);
+  const long B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
+  const long Hkv = k.size(2);
+  check_train_operand(dout, "dout", B, T, D);
+  check_train_operand(out, "out", B, T, D);
+  TORCH_CHECK(dout.size(2) == Hq && out.size(2) == Hq && out.is_contiguous(),
+              "attn_train_bwd: dout/out must be (B, T, Hq, D), out contiguous");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
+              lse.is_contiguous() && lse.dim() == 3 && lse.size(0) == B &&
+              lse.size(1) == Hq && lse.size(2) == T,
+              "attn_train_bwd: lse must be contiguous f32 (B, Hq, T)");
+  TORCH_CHECK(dout.get_device() == q.get_device() &&
+              out.get_device() == q.get_device() &&
+              lse.get_device() == q.get_device(),
+              "attn_train_bwd: all tensors must share a device");
+  const float* alibi_ptr = train_alibi_ptr(alibi, q, Hq);
+  c10::DeviceGuard guard(q.device());
+  auto dq = torch::empty({B, T, Hq, D}, q.options());
+  auto dk = torch::empty({B, T, Hkv, D}, q.options());
+  auto dv = torch::empty({B, T, Hkv, D}, q.options());
+  auto delta = torch::empty({B, Hq, T}, lse.options());
+  const int ntile = (int)((T + TR_ROWS - 1) / TR_ROWS);
+  const int G = (int)(Hq / Hkv);
+  auto launch = [&](auto d) {
+    constexpr int DD = decltype(d)::value;
+    // delta is written by the dQ kernel and read by the dK/dV kernel:
+    // same stream, so the order is the launch order
+    attn_train_dq_kernel<DD><<<(unsigned)(B * Hq * ntile), 512, 0, cur_stream()>>>(
+        bf_ptr(dout), bf_ptr(q), bf_ptr(k), bf_ptr(v), bf_ptr(out),
+        lse.data_ptr<float>(), alibi_ptr, bf_ptr_mut(dq),
+        delta.data_ptr<float>(), (int)Hq, G, (int)T, ntile, (int)window,
+        (float)scale, dout.stride(0), dout.stride(1), dout.stride(2),
+        q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
+        k.stride(2), v.stride(0), v.stride(1), v.stride(2));
+    attn_train_dkdv_kernel<DD><<<(unsigned)(B * Hkv * ntile), 512, 0, cur_stream()>>>(
+        bf_ptr(dout), bf_ptr(q), bf_ptr(k), bf_ptr(v), lse.data_ptr<float>(),
+        delta.data_ptr<float>(), alibi_ptr, bf_ptr_mut(dk), bf_ptr_mut(dv),
+        (int)Hq, G, (int)T, ntile, (int)window, (float)scale,
+        dout.stride(0), dout.stride(1), dout.stride(2),
+        q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
+        k.stride(2), v.stride(0), v.stride(1), v.stride(2));
+  };
+  if (D == 128) launch(std::integral_constant<int, 128>{});
+  else launch(std::integral_constant<int, 64>{});
+  return {dq, dk, dv};
+}
+
 // Fused RoPE + paged-KV write on the raw QKV GEMM output.
 void rope_kv_write_(torch::Tensor qkv, long Hq_, long Hkv_, torch::Tensor cos_t,
                     torch::Tensor sin_t, c10::optional<torch::Tensor> pos,
@@ -1199,6 +1324,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_prefill_qkv", &attn_prefill_qkv);
   m.def("rope_kv_write_", &rope_kv_write_);
   m.def("attn_prefill", &attn_prefill);
+  m.def("attn_train_fwd", &attn_train_fwd);
+  m.def("attn_train_bwd", &attn_train_bwd);
   m.def("gemm_skinny", &gemm_skinny, py::arg("A"), py::arg("W"),
         py::arg("residual") = c10::nullopt, py::arg("bias") = c10::nullopt,
         py::arg("ksplit") = 0, py::arg("norm_w") = c10::nullopt,

@@ -686,3 +686,62 @@ def quant4_unpack(packed, scale, zero, dtype=torch.bfloat16):
 def mfma_selftest(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     _require_ext()
     return hip_ops.mfma_selftest(A.contiguous(), B.contiguous())
+
+
+# ---------------------------------------------------------------------------
+# training attention
+# ---------------------------------------------------------------------------
+
+
+class _AttnTrainFn(torch.autograd.Function):
+    """Flash forward/backward over ops/hip/attn_train.hip. Saves q, k, v, the
+    bf16 output and the per-row LSE; nothing quadratic in T is kept."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale, window, alibi):
+        want = any(ctx.needs_input_grad[:3])
+        out, lse = hip_ops.attn_train_fwd(q, k, v, scale, window, alibi, want)
+        if want:
+            ctx.save_for_backward(q, k, v, out, lse,
+                                  alibi if alibi is not None else q.new_empty(0))
+            ctx.has_alibi = alibi is not None
+            ctx.scale, ctx.window = scale, window
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, alibi = ctx.saved_tensors
+        if dout.stride(-1) != 1 or any(s % 8 for s in dout.stride()[:-1]):
+            dout = dout.contiguous()
+        dq, dk, dv = hip_ops.attn_train_bwd(
+            dout, q, k, v, out, lse, ctx.scale, ctx.window,
+            alibi if ctx.has_alibi else None)
+        return dq, dk, dv, None, None, None
+
+
+def _train_view_ok(t: torch.Tensor) -> bool:
+    return (t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1])
+            and t.storage_offset() % 8 == 0)
+
+
+def attn_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
+               window: int = 0,
+               alibi_slopes: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Differentiable causal attention for the fine-tuning path.
+
+    q (B, T, Hq, D), k/v (B, T, Hkv, D) -> (B, T, Hq, D); see
+    reference.attn_train for the definition. bf16 device tensors with
+    D in {64, 128} run the gfx950 kernels (BBAMD_TRAIN_ATTN_KERNEL=0, read
+    per call, turns them off); everything else — CPU, fp32, larger D —
+    takes the torch composition."""
+    D = q.shape[-1]
+    if (_on_gpu(q) and q.dtype == torch.bfloat16 and D in (64, 128)
+            and os.environ.get("BBAMD_TRAIN_ATTN_KERNEL", "1") != "0"):
+        _require_ext()
+        q, k, v = (t if _train_view_ok(t) else t.contiguous() for t in (q, k, v))
+        alibi = None
+        if alibi_slopes is not None:
+            alibi = alibi_slopes.detach().to(device=q.device,
+                                             dtype=torch.float32).contiguous()
+        return _AttnTrainFn.apply(q, k, v, float(scale), int(window), alibi)
+    return ref.attn_train(q, k, v, scale, window, alibi_slopes)

@@ -494,3 +494,36 @@ def moe_gemm_grouped(A: torch.Tensor, W: torch.Tensor, off: torch.Tensor,
             y = y * scale[slots].float().unsqueeze(1)
         C[slots] = y.to(A.dtype)
     return C
+
+
+def attn_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
+               window: int = 0,
+               alibi_slopes: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Differentiable full-sequence attention (the training path's definition;
+    ops/hip/attn_train.hip is its kernel form).
+
+    q (B, T, Hq, D), k/v (B, T, Hkv, D) -> (B, T, Hq, D). Causal, with an
+    optional sliding window (key > query - window) and optional ALiBi slopes
+    (Hq,) added as slope[h] * key_index — softmax is shift invariant per row,
+    so the absolute start position does not enter. fp32 scores and softmax."""
+    B, T, Hq, D = q.shape
+    G = Hq // k.shape[2]
+    q, k, v = (t.permute(0, 2, 1, 3) for t in (q, k, v))
+    if G > 1:
+        k = k.repeat_interleave(G, dim=1)
+        v = v.repeat_interleave(G, dim=1)
+    scores = torch.matmul(q.float(), k.float().transpose(-1, -2))
+    if scale != 1.0:
+        scores = scores * scale
+    if alibi_slopes is not None:
+        scores = scores + alibi_slopes.view(1, Hq, 1, 1).to(scores.device) * \
+            torch.arange(T, dtype=torch.float32,
+                         device=scores.device).view(1, 1, 1, T)
+    mask = torch.ones(T, T, dtype=torch.bool, device=scores.device).tril()
+    if window > 0:
+        pos = torch.arange(T, device=scores.device)
+        mask &= pos.view(1, T) > pos.view(T, 1) - window
+    scores = scores.masked_fill(~mask, float("-inf"))
+    p = torch.softmax(scores, dim=-1)
+    out = torch.matmul(p, v.float()).to(q.dtype)
+    return out.permute(0, 2, 1, 3)
