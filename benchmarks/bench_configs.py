@@ -5,7 +5,8 @@ harness exercises the remaining configs' machinery on one MI355X:
 
   offload  — llama-2-70b-class shard with FlexGen-style host offload
              (weight_gpu_percent, 4-bit host compression optional)
-  mixtral  — MoE decode (skinny grouped expert GEMMs)
+  mixtral  — MoE decode (skinny grouped expert GEMMs); mixtral_w4 the same
+             with quantize_q4 (4-bit weights, grouped W4 expert GEMMs)
   spec     — tree speculative decoding, local target+draft, acceptance rate
 
     python benchmarks/bench_configs.py offload mixtral spec
@@ -80,14 +81,28 @@ def bench_offload(steps=16):
                               "offloaded blocks"}))
 
 
-def bench_mixtral(steps=24):
+def _block_weight_bytes(stack):
+    """resident bytes of the blocks' parameters plus their 4-bit packs"""
+    n = 0
+    for blk in stack.blocks:
+        n += sum(p.numel() * p.element_size() for p in blk.parameters())
+        for packed, scale, zero, _ in (getattr(blk, "_w4", None) or {}).values():
+            n += sum(t.numel() * t.element_size() for t in (packed, scale, zero))
+    return n
+
+
+def bench_mixtral(steps=24, quantize_q4=False, B=16):
     from bloombee_amd.engine import LocalEngine
 
     eng = LocalEngine("mixtral-tiny" if DEV == "cpu" else "mixtral-8x7b-4l",
-                      device=DEV, seed=0, kv_max_tokens=1 << 16)
-    tps, ms = _decode_loop(eng, B=16, prompt_len=64, steps=steps)
-    print(json.dumps({"config": "mixtral MoE decode", "tokens_per_s": round(tps, 1),
-                      "ms_per_step": round(ms, 2)}))
+                      device=DEV, seed=0, kv_max_tokens=1 << 16,
+                      quantize_q4=quantize_q4)
+    tps, ms = _decode_loop(eng, B=B, prompt_len=64, steps=steps)
+    print(json.dumps({"config": "mixtral MoE decode"
+                                + (" w4" if quantize_q4 else ""), "batch": B,
+                      "tokens_per_s": round(tps, 1),
+                      "ms_per_step": round(ms, 2),
+                      "block_weight_bytes": _block_weight_bytes(eng.stack)}))
 
 
 def bench_spec(steps=32, self_draft=False, draft_q4=False):
@@ -321,6 +336,7 @@ def bench_families(steps=24):
 
 
 ALL = {"offload": bench_offload, "mixtral": bench_mixtral,
+       "mixtral_w4": lambda: bench_mixtral(quantize_q4=True),
        "families": bench_families,
        "kv_multiplex": bench_kv_multiplex,
        "spec": bench_spec,

@@ -3,7 +3,7 @@
 Reports per-kernel time and effective HBM bandwidth / TFLOPs so kernel
 changes can be A/B'd without the end-to-end bench's noise.
 
-    python benchmarks/bench_kernels.py [attn_decode attn_mixed attn_prefill train_attn ...]
+    python benchmarks/bench_kernels.py [attn_decode attn_mixed attn_prefill train_attn moe_w4 ...]
 """
 import math
 import os
@@ -329,6 +329,75 @@ def bench_train_attn():
               f"bwd (dQ + dK/dV) {t_b*1e3:7.3f} ms {7*pair/t_b/1e12:6.1f} TF/s")
 
 
+def bench_moe_w4():
+    """Grouped expert GEMM, 4-bit weights (moe_gemm_w4.hip) beside the bf16
+    grouped kernel (moe_gemm.hip) at the Mixtral-8x7B shapes: E = 8, gate_up
+    N=28672 K=4096 and down N=4096 K=14336; 1, 4, 16, 32 tokens with top-2
+    routing spread round-robin over the experts. Three alternating rounds
+    per shape (median and spread). Each path cycles through enough copies of
+    its weights that a call never finds them in the 256 MB last-level cache.
+    TB/s is the bytes of the ACTIVE experts' weights (codes + scale + zero
+    for W4) over the time."""
+    E = 8
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    for N, K, tag in [(28672, 4096, "gate_up"), (4096, 14336, "down")]:
+        wb = torch.randn(E, N, K, generator=gen, device=DEV,
+                         dtype=torch.float32).mul_(K ** -0.5).to(torch.bfloat16)
+        packed, scale, zero = ops.quant4_pack(wb)
+        packed = packed.reshape(E, N, K // 2)
+        scale, zero = scale.reshape(E, N, K // 64), zero.reshape(E, N, K // 64)
+        w4_bytes = N * K // 2 + 4 * N * K // 64          # per expert
+        bf_bytes = N * K * 2
+        for T in (1, 4, 16, 32):
+            S = 2 * T
+            fe = (torch.arange(S) % E)                     # slot t*2+j -> expert
+            order = fe.argsort(stable=True)
+            counts = torch.bincount(fe, minlength=E)
+            active = int((counts > 0).sum())
+            off = torch.zeros(E + 1, dtype=torch.int32)
+            off[1:] = counts.cumsum(0).int()
+            off = off.to(DEV)
+            tok = (order // 2).int().to(DEV)
+            sc = torch.rand(S, device=DEV)
+            # gate_up gathers token rows; down consumes sorted slot rows
+            gather = tag == "gate_up"
+            a = torch.randn(T if gather else S, K, generator=gen, device=DEV,
+                            dtype=torch.float32).to(torch.bfloat16)
+            rm, ss = (tok, None) if gather else (None, sc)
+            mch = (T + 31) // 32
+            nrot4 = max(2, -(-(768 << 20) // (active * w4_bytes)))
+            nrotb = max(2, -(-(768 << 20) // (active * bf_bytes)))
+            nrot4, nrotb = min(nrot4, 12), min(nrotb, 4)
+            w4s = [(packed.clone(), scale.clone(), zero.clone()) for _ in range(nrot4)]
+            wbs = [wb.clone() for _ in range(nrotb)]
+            i4, ib = [0], [0]
+
+            def run4(ks=0):
+                p, s, z = w4s[i4[0] % nrot4]
+                i4[0] += 1
+                return ops.hip_ops.moe_gemm_w4(a, p, s, z, off, rm, ss, S, mch, ks)
+
+            def runb():
+                w = wbs[ib[0] % nrotb]
+                ib[0] += 1
+                return ops.hip_ops.moe_gemm(a, w, off, rm, ss, S, mch)
+
+            t4, tb, t1 = [], [], []
+            for _ in range(3):
+                t4.append(_event_time(run4, 40, 8))
+                tb.append(_event_time(runb, 40, 8))
+                t1.append(_event_time(lambda: run4(1), 40, 8))
+            t4.sort(), tb.sort(), t1.sort()
+            print(f"moe_w4 {tag} E{E} N{N} K{K} T{T} ({active} active): "
+                  f"w4 {t4[1]*1e6:7.1f} us [{t4[0]*1e6:.1f}..{t4[2]*1e6:.1f}] "
+                  f"{active*w4_bytes/t4[1]/1e12:5.2f} TB/s   "
+                  f"w4 ksplit=1 {t1[1]*1e6:7.1f} us [{t1[0]*1e6:.1f}..{t1[2]*1e6:.1f}]   "
+                  f"bf16 {tb[1]*1e6:7.1f} us [{tb[0]*1e6:.1f}..{tb[2]*1e6:.1f}] "
+                  f"{active*bf_bytes/tb[1]/1e12:5.2f} TB/s   "
+                  f"bf16/w4 {tb[1]/t4[1]:4.2f}", flush=True)
+            del w4s, wbs
+
+
 ALL = {
     "attn_decode": bench_attn_decode,
     "attn_mixed": bench_attn_mixed,
@@ -340,6 +409,7 @@ ALL = {
     "swiglu": bench_swiglu,
     "gemm": bench_gemm,
     "gemm_norm": bench_gemm_norm,
+    "moe_w4": bench_moe_w4,
 }
 
 if __name__ == "__main__":

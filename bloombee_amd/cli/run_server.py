@@ -74,9 +74,12 @@ def main():
                     choices=["bfloat16", "float32"],
                     help="serve dtype (kernels are bf16; float32 = CPU path)")
     ap.add_argument("--quant-type", default="none",
-                    choices=["none", "nf4"],
+                    choices=["none", "nf4", "w4"],
                     help="nf4 maps to the 4-bit host weight tier "
-                         "(compress_weight); LLM.int8 is not supported")
+                         "(compress_weight); w4 quantizes the resident "
+                         "weights and decodes through the 4-bit weight-stream "
+                         "kernels (llama, qwen3, mixtral; not with weight "
+                         "offload); LLM.int8 is not supported")
     args = ap.parse_args()
 
     if args.max_chunk_tokens is not None:
@@ -122,6 +125,7 @@ def main():
         max_batch_size=args.max_batch_size,
         announce_host=args.announce_host,
         announce_port=args.announce_port,
+        quantize_q4=args.quant_type == "w4",
     )
     server.run()
 

@@ -62,7 +62,74 @@ class MixtralBlock(torch.nn.Module):
                                     device=dev).mul_(std).to(w.dtype))
         return self
 
+    # -- 4-bit weights ----------------------------------------------------
+    @torch.no_grad()
+    def quantize_weights_q4(self, keep_full: bool = False):
+        """Pack qkv_w, o_w and both expert weight stacks into 4-bit group
+        codes (quant4_pack layout, experts keep their leading dimension);
+        the router and the norms stay bf16. Decode then streams ~3.5x fewer
+        bytes: the attention projections through ops.linear_w4, the grouped
+        expert GEMMs through ops.moe_gemm_grouped_w4. keep_full=False drops
+        the bf16 weights (the block becomes inference-only)."""
+        self._w4 = {}
+        for name in ("qkv_w", "o_w", "expert_gate_up_w", "expert_down_w"):
+            w = getattr(self, name).detach()
+            packed, scale, zero = ops.quant4_pack(w)
+            lead = tuple(w.shape[:-1])
+            self._w4[name] = (packed.reshape(*lead, -1).contiguous(),
+                              scale.reshape(*lead, -1).half().contiguous(),
+                              zero.reshape(*lead, -1).half().contiguous(),
+                              w.shape[-2])
+            if not keep_full:
+                getattr(self, name).data = torch.empty(
+                    0, dtype=w.dtype, device=w.device)
+        return self
+
+    def _lin(self, x, w, name):
+        """ops.linear, or the 4-bit weight-stream kernel on a quantized
+        block (quantize_weights_q4)."""
+        w4 = getattr(self, "_w4", None)
+        if w4 is not None and name in w4:
+            packed, scale, zero, N = w4[name]
+            return ops.linear_w4(x, packed, scale, zero, N)
+        return ops.linear(x, w)
+
+    def _expert_w(self, name, le, dtype):
+        """Local expert le's weight matrix; dequantized on a quantized block."""
+        w4 = getattr(self, "_w4", None)
+        if w4 is None or name not in w4:
+            return getattr(self, name)[le]
+        packed, scale, zero, N = w4[name]
+        G = scale.shape[-1]
+        return ops.quant4_unpack(packed[le].reshape(N * G, 32),
+                                 scale[le].reshape(-1), zero[le].reshape(-1),
+                                 dtype=dtype).reshape(N, G * 64).to(dtype)
+
     # -- MoE MLP ----------------------------------------------------------
+    def _grouped_experts(self, flat, off, tok, wsorted) -> torch.Tensor:
+        """Both expert GEMMs as grouped launches over expert-sorted slots
+        (off / tok / wsorted on device: prefix sums, slot -> token, slot
+        routing weight), SwiGLU between them and the scatter-add back to
+        tokens. Shapes depend on the token count only: no host sync."""
+        Tk = tok.numel()
+        mch = (flat.shape[0] + 31) // 32
+        w4 = getattr(self, "_w4", None)
+        if w4 is not None:
+            gu = ops.moe_gemm_grouped_w4(
+                flat, *w4["expert_gate_up_w"][:3], off, rowmap=tok,
+                S=Tk, mchunks=mch)
+            dn = ops.moe_gemm_grouped_w4(
+                ops.swiglu(gu), *w4["expert_down_w"][:3], off,
+                slot_scale=wsorted, S=Tk, mchunks=mch)
+        else:
+            gu = ops.moe_gemm_grouped(flat, self.expert_gate_up_w, off,
+                                      rowmap=tok, S=Tk, mchunks=mch)
+            dn = ops.moe_gemm_grouped(ops.swiglu(gu), self.expert_down_w,
+                                      off, scale=wsorted, S=Tk, mchunks=mch)
+        out = torch.zeros_like(flat)
+        out.index_add_(0, tok.long(), dn)
+        return out
+
     def _moe(self, y: torch.Tensor) -> torch.Tensor:
         B, T, H = y.shape
         flat = y.reshape(-1, H)
@@ -78,7 +145,6 @@ class MixtralBlock(torch.nn.Module):
             # device and run BOTH expert GEMMs as single grouped launches
             # (ops/hip/moe_gemm.hip) — no per-expert host sync, no
             # per-expert kernel launches (BASELINE config 4)
-            Tk = flat.shape[0] * self.topk
             fe = experts.reshape(-1)
             order = fe.argsort(stable=True)
             counts = torch.bincount(fe, minlength=self.E)
@@ -87,14 +153,7 @@ class MixtralBlock(torch.nn.Module):
             off[1:] = counts.cumsum(0).int()
             tok = (order // self.topk).int()
             wsorted = weights.reshape(-1)[order].float()
-            mch = (flat.shape[0] + 31) // 32
-            gu = ops.moe_gemm_grouped(flat, self.expert_gate_up_w, off,
-                                      rowmap=tok, S=Tk, mchunks=mch)
-            dn = ops.moe_gemm_grouped(ops.swiglu(gu), self.expert_down_w,
-                                      off, scale=wsorted, S=Tk, mchunks=mch)
-            out = torch.zeros_like(flat)
-            out.index_add_(0, tok.long(), dn)
-            return out.view(B, T, H)
+            return self._grouped_experts(flat, off, tok, wsorted).view(B, T, H)
         out = torch.zeros_like(flat)
         # expert-parallel mode (parallel/expert.py): this rank holds only
         # experts [e0, e1); partial sums cross ranks via one all-reduce
@@ -104,8 +163,10 @@ class MixtralBlock(torch.nn.Module):
             if rows.numel() == 0:
                 continue
             xe = flat[rows]
-            h = ops.linear(ops.swiglu(ops.linear(xe, self.expert_gate_up_w[le])),
-                           self.expert_down_w[le])
+            h = ops.linear(
+                ops.swiglu(ops.linear(
+                    xe, self._expert_w("expert_gate_up_w", le, xe.dtype))),
+                self._expert_w("expert_down_w", le, xe.dtype))
             w = (weights * sel.to(weights.dtype)).sum(-1)[rows]
             out.index_add_(0, rows, h * w.unsqueeze(-1))
         if getattr(self, "ep_enabled", False):
@@ -121,7 +182,7 @@ class MixtralBlock(torch.nn.Module):
         Hq, Hkv = self.Hq, self.Hkv
         cfg = self.config
         x = ops.rms_norm(hidden, self.input_norm_w, cfg.rms_norm_eps)
-        qkv = ops.linear(x, self.qkv_w)
+        qkv = self._lin(x, self.qkv_w, "qkv_w")
         cos, sin = self.rope.get(hidden.device)
         kp = kv.k_pages(self.layer_index)
         vp = kv.v_pages(self.layer_index)
@@ -145,11 +206,16 @@ class MixtralBlock(torch.nn.Module):
         else:
             attn = ops.attn_paged_qkv(qkv, Hq, Hkv, kp, vp, pt, start_pos,
                                       self.scale)
-        a = ops.linear(attn, self.o_w)
+        a = self._lin(attn, self.o_w, "o_w")
         h2, y = ops.rms_norm_residual(a, hidden, self.post_norm_w, cfg.rms_norm_eps)
         return h2 + self._moe(y)
 
     def forward_train(self, hidden: torch.Tensor, start_pos: int = 0) -> torch.Tensor:
+        if self.qkv_w.numel() == 0:
+            raise RuntimeError(
+                "forward_train needs the bf16 weights: this block was "
+                "quantized with quantize_weights_q4(keep_full=False) and is "
+                "inference-only")
         B, T, H = hidden.shape
         Hq, Hkv, D = self.Hq, self.Hkv, self.D
         cfg = self.config

@@ -28,6 +28,7 @@ from bloombee_amd.ops.interface import (  # noqa: F401
     linear_w4,
     mfma_selftest,
     moe_gemm_grouped,
+    moe_gemm_grouped_w4,
     quant4_pack,
     quant4_unpack,
     rms_norm,

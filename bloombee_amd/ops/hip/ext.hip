@@ -21,6 +21,7 @@
 #include "gemm_skinny.hip"
 #include "moe_gemm.hip"
 #include "w4_gemm.hip"
+#include "moe_gemm_w4.hip"
 #include "mfma_selftest.hip"
 #include "quant4.hip"
 #include "wire.h"
@@ -906,6 +907,96 @@ torch::Tensor moe_gemm(torch::Tensor A, torch::Tensor W, torch::Tensor off,
 }
 
 
+// The ksplit rule of moe_gemm_w4 (0 = this rule), normalised like gemm_w4's:
+// the W4 stream is latency-bound below ~1800 blocks. The host cannot know
+// how many experts are active without a sync; min(E, S) bounds it.
+static int moe_w4_ksplit(int E, int N, int K, long S, long ksplit_req,
+                         int* kchunk) {
+  int ksplit = (int)ksplit_req;
+  if (ksplit <= 0) {
+    const long blocks = (long)(N / 64) * std::max<long>(1, std::min<long>(E, S));
+    ksplit = (int)std::max<long>(1, std::min<long>(K / 512, 1792 / blocks));
+  }
+  // groups of 64 must not straddle splits; slices of 128 keep the k-loop
+  // tail-free
+  const int nch = K / 128;
+  const int per = (nch + ksplit - 1) / ksplit;
+  *kchunk = per * 128;
+  return (nch + per - 1) / per;
+}
+
+// C(S,N) = (A[row(s)] @ dequant4(Wq[expert(s)])^T) * slot_scale[s] — grouped
+// decode MoE over 4-bit weights (moe_gemm_w4.hip). packed (E, N, K/2) u8,
+// scale / zero (E, N, K/64) f16 in quant4_pack layout; off, rowmap,
+// slot_scale, S and mchunks as for moe_gemm. ksplit as for gemm_w4 (0 = the
+// op's own rule).
+torch::Tensor moe_gemm_w4(torch::Tensor A, torch::Tensor packed,
+                          torch::Tensor scale, torch::Tensor zero,
+                          torch::Tensor off,
+                          c10::optional<torch::Tensor> rowmap,
+                          c10::optional<torch::Tensor> slot_scale,
+                          long S, long mchunks, long ksplit_req) {
+  CHECK_DEV(A); CHECK_BF16(A); CHECK_CONTIG(A);
+  CHECK_DEV_ALL3(packed, scale, zero);
+  CHECK_CONTIG(packed); CHECK_CONTIG(scale); CHECK_CONTIG(zero);
+  CHECK_DEV(off);
+  TORCH_CHECK(packed.scalar_type() == at::kByte &&
+              scale.scalar_type() == at::kHalf &&
+              zero.scalar_type() == at::kHalf,
+              "packed must be u8, scale and zero f16");
+  TORCH_CHECK(packed.dim() == 3, "packed must be (E, N, K/2)");
+  const int E = packed.size(0), N = packed.size(1);
+  const int K = (int)packed.size(2) * 2;
+  TORCH_CHECK(A.dim() == 2 && A.size(1) == K, "A/packed K mismatch");
+  TORCH_CHECK(K % 128 == 0 && N % 64 == 0, "K%128, N%64 required");
+  TORCH_CHECK(scale.numel() == (long)E * N * (K / 64) &&
+              zero.numel() == scale.numel(), "scale/zero shape mismatch");
+  TORCH_CHECK(off.scalar_type() == at::kInt && off.is_contiguous() &&
+              off.numel() == E + 1);
+  TORCH_CHECK(S >= 0 && mchunks >= 1 && ksplit_req >= 0);
+  const int* rmp = nullptr;
+  if (rowmap.has_value()) {
+    TORCH_CHECK(rowmap->scalar_type() == at::kInt &&
+                rowmap->is_contiguous() && rowmap->numel() == S);
+    CHECK_DEV((*rowmap));
+    rmp = rowmap->data_ptr<int>();
+  }
+  const float* sp = nullptr;
+  if (slot_scale.has_value()) {
+    TORCH_CHECK(slot_scale->scalar_type() == at::kFloat &&
+                slot_scale->is_contiguous() && slot_scale->numel() == S);
+    CHECK_DEV((*slot_scale));
+    sp = slot_scale->data_ptr<float>();
+  }
+  auto C = torch::empty({S, (long)N}, A.options());
+  if (S == 0) return C;
+  int kchunk = 0;
+  const int ksplit = moe_w4_ksplit(E, N, K, S, ksplit_req, &kchunk);
+  torch::Tensor part;
+  float* pp = nullptr;
+  if (ksplit > 1) {
+    part = torch::empty({(long)ksplit, S, (long)N},
+                        A.options().dtype(at::kFloat));
+    pp = part.data_ptr<float>();
+  }
+  dim3 grid(N / 64, (unsigned)(E * mchunks), ksplit);
+  TORCH_CHECK(grid.y <= 65535, "E * mchunks exceeds the grid limit");
+  moe_gemm_w4_kernel<2><<<grid, 256, 0, cur_stream()>>>(
+      bf_ptr(A), packed.data_ptr<unsigned char>(),
+      reinterpret_cast<const __half*>(scale.data_ptr()),
+      reinterpret_cast<const __half*>(zero.data_ptr()),
+      off.data_ptr<int>(), rmp, sp, bf_ptr_mut(C), pp,
+      (int)S, N, K, (int)mchunks, kchunk);
+  if (ksplit > 1) {
+    const long total4 = S * N / 4;
+    const int cgrid = (int)std::min<long>((total4 + 255) / 256, 2048);
+    moe_gemm_w4_combine_kernel<<<cgrid, 256, 0, cur_stream()>>>(
+        pp, off.data_ptr<int>() + E, sp, bf_ptr_mut(C), (int)S, N, ksplit);
+  }
+  return C;
+}
+
+
 // C(M,N) = A @ dequant4(Wq)^T [+R] [+bias], M <= 32 (w4_gemm.hip). Wq/scale/
 // zero in quant4_pack layout (2 codes/byte along K, f16 scale+zero per group
 // of 64). ~3.5x less weight-stream bytes than the bf16 kernel.
@@ -1338,6 +1429,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_kv_write_part", &rope_kv_write_part);
   m.def("moe_gemm", &moe_gemm);
   m.def("gemm_w4", &gemm_w4);
+  m.def("moe_gemm_w4", &moe_gemm_w4);
   m.def("quant4_pack", &quant4_pack);
   m.def("quant4_unpack", &quant4_unpack);
   m.def("mfma_selftest", &mfma_selftest);

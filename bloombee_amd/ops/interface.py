@@ -637,6 +637,48 @@ def moe_gemm_grouped(A: torch.Tensor, W: torch.Tensor, off: torch.Tensor,
     return ref.moe_gemm_grouped(A, W, off, rowmap, scale, S)
 
 
+def moe_gemm_grouped_w4(A: torch.Tensor, packed: torch.Tensor,
+                        scale: torch.Tensor, zero: torch.Tensor,
+                        off: torch.Tensor,
+                        rowmap: Optional[torch.Tensor] = None,
+                        slot_scale: Optional[torch.Tensor] = None,
+                        S: Optional[int] = None,
+                        mchunks: Optional[int] = None) -> torch.Tensor:
+    """moe_gemm_grouped over 4-bit expert weights (moe_gemm_w4.hip):
+    C[s] = (A[row(s)] @ dequant4(W[expert(s)])^T) (* slot_scale[s]).
+
+    packed (E, N, K/2) u8, scale / zero (E, N, K/64) f16: quant4_pack layout
+    with a leading expert dimension. off, rowmap, S and mchunks as for
+    moe_gemm_grouped. bf16 device activations with K % 128 == 0 and
+    N % 64 == 0 run the kernel, which streams ~3.5x fewer weight bytes and
+    computes in f16 (activations outside the f16 range are not supported,
+    as for linear_w4). Everything else, and BBAMD_MOE_W4_KERNEL=0 (read per
+    call), dequantizes the active experts and uses moe_gemm_grouped."""
+    E, N, Kh = packed.shape
+    K = Kh * 2
+    if S is None:
+        S = int(rowmap.numel()) if rowmap is not None else int(A.shape[0])
+    if mchunks is None:
+        mchunks = (int(A.shape[0]) + 31) // 32
+    if (_on_gpu(A) and A.dtype == torch.bfloat16 and K % 128 == 0
+            and N % 64 == 0
+            and os.environ.get("BBAMD_MOE_W4_KERNEL", "1") != "0"):
+        _require_ext()
+        return hip_ops.moe_gemm_w4(A.contiguous(), packed.contiguous(),
+                                   scale.half().contiguous(),
+                                   zero.half().contiguous(), off.int(),
+                                   rowmap, slot_scale, S, mchunks, 0)
+    if _on_gpu(A):
+        # the composition on device: dequantize every expert with the unpack
+        # kernel (no host sync on the group sizes) and run the bf16 kernel
+        _require_ext()
+        W = quant4_unpack(packed.reshape(-1, 32), scale.reshape(-1),
+                          zero.reshape(-1)).reshape(E, N, K).to(A.dtype)
+        return moe_gemm_grouped(A, W, off, rowmap, slot_scale, S, mchunks)
+    return ref.moe_gemm_grouped_w4(A, packed, scale, zero, off, rowmap,
+                                   slot_scale, S)
+
+
 def linear_w4(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor,
               zero: torch.Tensor, N: int,
               residual: Optional[torch.Tensor] = None,

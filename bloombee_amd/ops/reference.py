@@ -496,6 +496,29 @@ def moe_gemm_grouped(A: torch.Tensor, W: torch.Tensor, off: torch.Tensor,
     return C
 
 
+def moe_gemm_grouped_w4(A: torch.Tensor, packed: torch.Tensor,
+                        scale: torch.Tensor, zero: torch.Tensor,
+                        off: torch.Tensor,
+                        rowmap: Optional[torch.Tensor] = None,
+                        slot_scale: Optional[torch.Tensor] = None,
+                        S: Optional[int] = None) -> torch.Tensor:
+    """Reference for the grouped expert GEMM over 4-bit weights
+    (ops/hip/moe_gemm_w4.hip): moe_gemm_grouped on dequantized experts.
+    packed (E, N, K/2) u8, scale / zero (E, N, K/64) in quant4_pack layout
+    with a leading expert dimension. Only experts that own a slot are
+    dequantized (to A's dtype, which is what the block's loop multiplies by)."""
+    E, N, Kh = packed.shape
+    K = Kh * 2
+    offs = off.tolist()
+    W = torch.zeros(E, N, K, dtype=A.dtype, device=A.device)
+    for e in range(E):
+        if offs[e + 1] > offs[e]:
+            W[e] = quant4_unpack(packed[e].reshape(N, K // 64, 32),
+                                 scale[e].reshape(N, K // 64),
+                                 zero[e].reshape(N, K // 64), A.dtype)
+    return moe_gemm_grouped(A, W, off, rowmap, slot_scale, S)
+
+
 def attn_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
                window: int = 0,
                alibi_slopes: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -39,15 +39,32 @@ class StackBackend:
                  kv_max_tokens: int = 1 << 18,
                  checkpoint_dir: Optional[str] = None,
                  offload_policy=None,
-                 max_batch_size: int = 2048):
+                 max_batch_size: int = 2048,
+                 quantize_q4: bool = False):
         self.config = config
         self.start, self.end = start, end
         self.device = torch.device(device)
+        if (quantize_q4 and offload_policy is not None
+                and offload_policy.offloads_weights):
+            raise ValueError(
+                "quantize_q4 cannot be combined with weight offload: the "
+                "offload arena copies bf16 tensors")
         self.stack = BlockStack(config, start, end, device=device, seed=seed)
         if checkpoint_dir is not None:
             from bloombee_amd.server.from_pretrained import load_block_weights
             for i, blk in enumerate(self.stack.blocks):
                 load_block_weights(blk, checkpoint_dir, start + i)
+        if quantize_q4:
+            # compute-path 4-bit weights (w4_gemm.hip / moe_gemm_w4.hip);
+            # unlike LocalEngine a server refuses rather than serving bf16
+            # under a flag that asked for W4
+            for blk in self.stack.blocks:
+                if not hasattr(blk, "quantize_weights_q4"):
+                    raise ValueError(
+                        f"quantize_q4: model family {config.model_type!r} has "
+                        "no 4-bit compute path")
+            for blk in self.stack.blocks:
+                blk.quantize_weights_q4()
         if offload_policy is not None and offload_policy.offloads_weights:
             from bloombee_amd.offload.weights import OffloadedBlockStack
             self.stack = OffloadedBlockStack(self.stack, offload_policy)

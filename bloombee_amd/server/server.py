@@ -55,6 +55,7 @@ class Server:
         max_batch_size: int = 2048,
         announce_host: Optional[str] = None,
         announce_port: Optional[int] = None,
+        quantize_q4: bool = False,
     ):
         self.config = model if isinstance(model, ModelConfig) else resolve_config(model)
         self.model_name = model_name or (model if isinstance(model, str)
@@ -113,7 +114,8 @@ class Server:
                                 kv_max_tokens=kv_max_tokens,
                                 checkpoint_dir=checkpoint_dir,
                                 offload_policy=offload_policy,
-                                max_batch_size=max_batch_size)
+                                max_batch_size=max_batch_size,
+                                quantize_q4=quantize_q4)
         self.backend = StackBackend(self.config, block_indices[0],
                                     block_indices[1], **self._backend_kw)
         if adapters:
