@@ -163,6 +163,17 @@ def _sparse_kernel_ok(D: int, P: int) -> bool:
     return _SPARSE_KERNEL and D in (64, 128, 256) and P == 16
 
 
+def _alibi_on(alibi_slopes, dev):
+    """The slopes as the kernels take them: contiguous f32 on dev, or None."""
+    if alibi_slopes is None:
+        return None
+    return alibi_slopes.float().to(dev).contiguous()
+
+
+def _window_or_none(window: int):
+    return window if window > 0 else None
+
+
 def attn_decode(
     q, k_pages, v_pages, page_table, ctx_lens, scale: Optional[float] = None,
     window: int = 0, n_split: int = 0, alibi_slopes=None,
@@ -173,8 +184,7 @@ def attn_decode(
     if _attn_sparsity < 1.0 and window <= 0:
         if _on_gpu(q) and _sparse_kernel_ok(q.shape[-1], k_pages.shape[2]):
             _require_ext()
-            al = (alibi_slopes.float().to(q.device).contiguous()
-                  if alibi_slopes is not None else None)
+            al = _alibi_on(alibi_slopes, q.device)
             return hip_ops.attn_decode_sparse(
                 q.contiguous(), k_pages, v_pages, page_table, ctx_lens.int(),
                 _attn_sparsity, scale, al)
@@ -188,15 +198,14 @@ def attn_decode(
             # (D=512 runs attn_decode_wide_kernel — d split across waves)
             return ref.attn_paged(q, k_pages, v_pages, page_table,
                                   ctx_lens.long() - 1, scale,
-                                  sliding_window=window if window > 0 else None,
+                                  sliding_window=_window_or_none(window),
                                   alibi_slopes=alibi_slopes)
-        al = (alibi_slopes.float().to(q.device).contiguous()
-              if alibi_slopes is not None else None)
+        al = _alibi_on(alibi_slopes, q.device)
         return hip_ops.attn_decode(q.contiguous(), k_pages, v_pages, page_table,
                                    ctx_lens.int(), scale, window, n_split, al)
     q_start = ctx_lens.long() - 1
     return ref.attn_paged(q, k_pages, v_pages, page_table, q_start, scale,
-                          sliding_window=window if window > 0 else None,
+                          sliding_window=_window_or_none(window),
                           alibi_slopes=alibi_slopes)
 
 
@@ -213,14 +222,13 @@ def attn_prefill(
         if q.shape[-1] > 256:
             return ref.attn_paged(q, k_pages, v_pages, page_table,
                                   q_start.long(), scale,
-                                  sliding_window=window if window > 0 else None,
+                                  sliding_window=_window_or_none(window),
                                   alibi_slopes=alibi_slopes)
-        al = (alibi_slopes.float().to(q.device).contiguous()
-              if alibi_slopes is not None else None)
+        al = _alibi_on(alibi_slopes, q.device)
         return hip_ops.attn_prefill(q.contiguous(), k_pages, v_pages, page_table,
                                     q_start.int(), scale, window, al, None)
     return ref.attn_paged(q, k_pages, v_pages, page_table, q_start, scale,
-                          sliding_window=window if window > 0 else None,
+                          sliding_window=_window_or_none(window),
                           alibi_slopes=alibi_slopes)
 
 
@@ -303,7 +311,7 @@ def attn_paged_qkv(qkv, Hq: int, Hkv: int, k_pages, v_pages, page_table,
                                         q_start.int(), scale, window)
     q = qkv[..., : Hq * D].view(B, T, Hq, D).permute(0, 2, 1, 3).contiguous()
     out = ref.attn_paged(q, k_pages, v_pages, page_table, q_start.long(), scale,
-                         sliding_window=window if window > 0 else None)
+                         sliding_window=_window_or_none(window))
     return out.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
 
 
@@ -318,7 +326,7 @@ def attn_paged(q, k_pages, v_pages, page_table, q_start, scale=None, window: int
             scale = 1.0 / math.sqrt(q.shape[-1])
         return ref.attn_paged(q, k_pages, v_pages, page_table, q_start, scale,
                               alibi_slopes=alibi_slopes,
-                              sliding_window=window if window > 0 else None)
+                              sliding_window=_window_or_none(window))
     if tree_mask is not None:
         if scale is None:
             scale = 1.0 / math.sqrt(q.shape[-1])
@@ -377,27 +385,18 @@ def linear(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = 
     if (_on_gpu(x) and M <= 32 and x.dtype == torch.bfloat16
             and K % 256 == 0 and N % 64 == 0):
         _require_ext()
-        if norm is not None or ss_out is not None:
-            nw = None
-            eps = 0.0
-            mode = 0
-            if norm is not None:
-                eps = float(norm[1])
-                if norm[0] is None:
-                    mode = 2  # weight pre-folded into W: invr-only scaling
-                else:
-                    nw = norm[0].contiguous()
-                    mode = 1
-            return hip_ops.gemm_skinny(x.contiguous(), w, residual, bias,
-                                       _INLAUNCH_KSPLIT if cnt is not None else 0,
-                                       nw, eps, ss_in, ss_out, mode,
-                                       defer_combine, cnt)
-        if defer_combine or cnt is not None:
-            return hip_ops.gemm_skinny(x.contiguous(), w, residual, bias,
-                                       _INLAUNCH_KSPLIT if cnt is not None else 0,
-                                       None, 0.0, None, None, 0,
-                                       defer_combine, cnt)
-        return hip_ops.gemm_skinny(x.contiguous(), w, residual, bias, 0)
+        nw, eps, mode = None, 0.0, 0
+        if norm is not None:
+            eps = float(norm[1])
+            if norm[0] is None:
+                mode = 2  # weight pre-folded into W: invr-only scaling
+            else:
+                nw = norm[0].contiguous()
+                mode = 1
+        return hip_ops.gemm_skinny(x.contiguous(), w, residual, bias,
+                                   _INLAUNCH_KSPLIT if cnt is not None else 0,
+                                   nw, eps, ss_in if norm is not None else None,
+                                   ss_out, mode, defer_combine, cnt)
     if defer_combine or cnt is not None:
         raise RuntimeError("defer_combine / cnt require the GPU skinny-GEMM "
                            "path (callers gate on fuse_norm_linear_ok)")
@@ -468,16 +467,7 @@ def fuse_swiglu_ok(x: torch.Tensor, gate_up_w: torch.Tensor) -> bool:
     (narrow 2I with K >= 1024) keep the separate kernels."""
     N, K = gate_up_w.shape[0], x.shape[-1]
     return (_FUSE_SWIGLU and fuse_norm_linear_ok(x, gate_up_w)
-            and _skinny_auto_ksplit(N, K) == 1)
-
-
-def _skinny_auto_ksplit(N: int, K: int) -> int:
-    """ksplit gemm_skinny picks for itself (ext.hip, ksplit_req == 0)."""
-    if N // 64 >= 256:
-        ks = int(os.environ.get("BBAMD_GEMM_KSPLIT_BIG", "1") or 1)
-    else:
-        ks = min(K // 512, max(1, min(8, 1024 // (N // 64))))
-    return max(1, ks)
+            and hip_ops.gemm_skinny_plan(N, K, 0)[0] == 1)
 
 
 def fuse_qkv_rope_ok(x: torch.Tensor, qkv_w: torch.Tensor, D: int) -> bool:
@@ -530,8 +520,7 @@ def _attn_mixed_gpu(q_or_qkv, q4, k_pages, v_pages, page_table, ctx_lens,
     B, Hq, _, D = q4.shape
     S_host = host_k.shape[2]
     dev = q4.device
-    al = (alibi_slopes.float().to(dev).contiguous()
-          if alibi_slopes is not None else None)
+    al = _alibi_on(alibi_slopes, dev)
     lo = 0
     if window > 0:
         # host suffix inside the window, per row (absolute positions)

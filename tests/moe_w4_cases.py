@@ -56,7 +56,7 @@ def ids(specs):
 
 
 # ---------------------------------------------------------------------------
-# host-side launch geometry (mirrors ext.hip moe_w4_ksplit; used only by the
+# host-side launch geometry (mirrors ext.hip moe_w4_plan; used only by the
 # mutations, never by `want`)
 # ---------------------------------------------------------------------------
 

@@ -672,8 +672,8 @@ def test_qwen3_block_fused_norm_matches_unfused():
 def test_gemm_w4_small_m_parity():
     """linear_w4 at M = 1..4 vs the dequantized F.linear reference. Only
     M == 1 runs the GEMV (gemm_w4 in ext.hip dispatches it for M == 1
-    alone); M = 2..4 exercise the split-K MFMA form. The GEMV's MROWS > 1
-    instantiations are not reachable from dispatch and not tested."""
+    alone); M = 2..4 exercise the split-K MFMA form. The GEMV is a
+    single-row kernel: its multi-row form was measured slower and removed."""
     torch.manual_seed(17)
     for M in (1, 2, 3, 4):
         for N, K in [(512, 2048), (1024, 4096), (256, 14336)]:
