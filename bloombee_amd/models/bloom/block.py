@@ -6,25 +6,22 @@ KV rides the same paged pools as every family."""
 from __future__ import annotations
 
 import math
-from typing import Optional
 
 import torch
 
 from bloombee_amd import ops
 from bloombee_amd.kv.paged import SessionHandle
 from bloombee_amd.models.base import ModelConfig
+from bloombee_amd.models.block_common import FamilyBlock, paged_attention
 
 
-class BloomBlock(torch.nn.Module):
+class BloomBlock(FamilyBlock):
     def __init__(self, config: ModelConfig, layer_index: int = 0, rope=None):
-        super().__init__()
-        self.config = config
-        self.layer_index = layer_index
+        super().__init__(config, layer_index)
         H = config.hidden_size
         D = config.head_dim
         Hq = config.num_attention_heads
         I = config.intermediate_size
-        dt = config.dtype
         self.Hq, self.D, self.I = Hq, D, I
         self.scale = 1.0 / math.sqrt(D)
         # buffer (not a plain attr) so .to(device) moves it once: a CPU
@@ -33,33 +30,13 @@ class BloomBlock(torch.nn.Module):
         # capture (the bloom capture fault isolated in r02)
         self.register_buffer("alibi", ops.alibi_slopes_for(Hq).float(),
                              persistent=False)
-
-        def p(*shape):
-            return torch.nn.Parameter(torch.empty(*shape, dtype=dt),
-                                      requires_grad=False)
-
+        p = self.p
         self.ln1_w, self.ln1_b = p(H), p(H)
         self.qkv_w, self.qkv_b = p(3 * Hq * D, H), p(3 * Hq * D)
         self.dense_w, self.dense_b = p(H, Hq * D), p(H)
         self.ln2_w, self.ln2_b = p(H), p(H)
         self.up_w, self.up_b = p(I, H), p(I)
         self.down_w, self.down_b = p(H, I), p(H)
-
-    @torch.no_grad()
-    def init_random(self, seed: Optional[int] = None):
-        s = seed if seed is not None else 1234 + self.layer_index
-        dev = self.ln1_w.device
-        gen = torch.Generator(device=dev).manual_seed(s)
-        std = 0.02 / math.sqrt(2 * self.config.num_hidden_layers)
-        for name, w in self.named_parameters():
-            if name.endswith("_b"):
-                w.zero_()
-            elif name.startswith("ln"):
-                w.fill_(1.0)
-            else:
-                w.copy_(torch.randn(w.shape, generator=gen, dtype=torch.float32,
-                                    device=dev).mul_(std).to(w.dtype))
-        return self
 
     def _attn(self, x: torch.Tensor, kv: SessionHandle,
               start_pos: torch.Tensor) -> torch.Tensor:
@@ -69,30 +46,17 @@ class BloomBlock(torch.nn.Module):
         q = qkv[..., :Hq * D].view(B, T, Hq, D).permute(0, 2, 1, 3).contiguous()
         k = qkv[..., Hq * D:2 * Hq * D].view(B, T, Hq, D).permute(0, 2, 1, 3).contiguous()
         v = qkv[..., 2 * Hq * D:].view(B, T, Hq, D).permute(0, 2, 1, 3).contiguous()
-        kp = kv.k_pages(self.layer_index)
-        vp = kv.v_pages(self.layer_index)
-        pt = kv.page_table()
-        ops.kv_write(k, v, kp, vp, pt, start_pos)
-        hp = (kv.host_prefix(self.layer_index)
-              if hasattr(kv, "host_prefix") else None)
-        if hp is not None:
-            # mixed-device session (kv.swap_in_as_prefix): host prefix on the
-            # CPU + device recent segment, exact merge. ALiBi positions are
-            # absolute — the op shifts the device segment by the prefix
-            # length; decode-only (backend gates T == 1)
-            out = ops.attn_paged_mixed(q, kp, vp, pt, start_pos + T,
-                                       hp[0], hp[1], self.scale,
-                                       alibi_slopes=self.alibi)
-        else:
-            out = ops.attn_paged(q, kp, vp, pt, start_pos.long(), self.scale,
-                                 alibi_slopes=self.alibi)
-        out = out.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
+        ops.kv_write(k, v, kv.k_pages(self.layer_index),
+                     kv.v_pages(self.layer_index), kv.page_table(), start_pos)
+        out = paged_attention(q, kv, self.layer_index, start_pos, self.scale,
+                              alibi_slopes=self.alibi)
         return ops.linear(out, self.dense_w, bias=self.dense_b)
 
     @torch.no_grad()
     def forward_inference(self, hidden: torch.Tensor, kv: SessionHandle,
-                          start_pos: torch.Tensor,
-                          position_ids=None) -> torch.Tensor:
+                          start_pos: torch.Tensor, position_ids=None,
+                          tree_mask=None) -> torch.Tensor:
+        self._no_tree_mask(tree_mask)
         cfg = self.config
         x = ops.layer_norm(hidden, self.ln1_w, self.ln1_b, cfg.layer_norm_epsilon)
         h = hidden + self._attn(x, kv, start_pos)
@@ -125,6 +89,3 @@ class BloomBlock(torch.nn.Module):
         g = torch.nn.functional.gelu(u.float(), approximate="tanh").to(u.dtype)
         m = torch.nn.functional.linear(g, self.down_w, self.down_b)
         return h + m
-
-    def forward(self, *args, **kw):
-        return self.forward_inference(*args, **kw)

@@ -4,13 +4,14 @@ every norm is plain-weight RMS (Gemma-4 dropped the (1+w) convention);
 attention scaling is 1.0."""
 from __future__ import annotations
 
-import math
 from typing import Optional
 
 import torch
 
 from bloombee_amd import ops
 from bloombee_amd.kv.paged import SessionHandle
+from bloombee_amd.models.block_common import (FamilyBlock, paged_attention,
+                                              rotary_positions)
 from bloombee_amd.models.gemma4.config import Gemma4Config
 from bloombee_amd.ops import reference as refops
 from bloombee_amd.ops.reference import rope_cos_sin
@@ -43,11 +44,9 @@ def _rope_partial(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
     return out.to(x.dtype)
 
 
-class Gemma4Block(torch.nn.Module):
+class Gemma4Block(FamilyBlock):
     def __init__(self, config: Gemma4Config, layer_index: int = 0, rope=None):
-        super().__init__()
-        self.config = config
-        self.layer_index = layer_index          # global at init; BlockStack
+        super().__init__(config, layer_index)   # global at init; BlockStack
         self.global_index = layer_index         # rebases layer_index locally
         H = config.hidden_size
         self.Hq = config.num_attention_heads
@@ -59,18 +58,13 @@ class Gemma4Block(torch.nn.Module):
         self.I = config.intermediate_size
         self.k_eq_v = bool(config.extras.get("attention_k_eq_v", False))
         self.donor = config.shared_kv_donor(layer_index)
-        dt = config.dtype
         Hq, Hkv, D = self.Hq, self.Hkv, self.D
 
         cos, sin = rope_cos_sin(self.rot_dim, config.max_position_embeddings,
                                 theta=theta)
         self._cos, self._sin = cos, sin
         self._rope_cache = {}
-
-        def p(*shape):
-            return torch.nn.Parameter(torch.empty(*shape, dtype=dt),
-                                      requires_grad=False)
-
+        p = self.p
         self.input_norm_w = p(H)
         self.post_attn_norm_w = p(H)
         self.pre_ffn_norm_w = p(H)
@@ -100,35 +94,17 @@ class Gemma4Block(torch.nn.Module):
         return self._rope_cache[key]
 
     @torch.no_grad()
-    def init_random(self, seed: Optional[int] = None):
-        s = seed if seed is not None else 1234 + self.global_index
-        dev = self.input_norm_w.device
-        gen = torch.Generator(device=dev).manual_seed(s)
-        std = 0.02 / math.sqrt(2 * self.config.num_hidden_layers)
-        for name, w in self.named_parameters():
-            if name.endswith("norm_w"):
-                w.fill_(1.0)
-            else:
-                w.copy_(torch.randn(w.shape, generator=gen, dtype=torch.float32,
-                                    device=dev).mul_(std).to(w.dtype))
-        return self
-
-    @torch.no_grad()
     def forward_inference(self, hidden: torch.Tensor, kv: SessionHandle,
-                          start_pos: torch.Tensor,
-                          position_ids=None) -> torch.Tensor:
+                          start_pos: torch.Tensor, position_ids=None,
+                          tree_mask=None) -> torch.Tensor:
+        self._no_tree_mask(tree_mask)
         B, T, H = hidden.shape
         Hq, Hkv, D = self.Hq, self.Hkv, self.D
         cfg = self.config
         eps = cfg.rms_norm_eps
         cos, sin = self._tables(hidden.device)
-        if position_ids is None:
-            # mixed-device sessions: start_pos is local to the device pool,
-            # rotary positions stay absolute (kv.pos_offset, see llama block)
-            pos = (start_pos.view(B, 1).long() + getattr(kv, "pos_offset", 0)
-                   + torch.arange(T, device=hidden.device).view(1, T))
-        else:
-            pos = position_ids.long()
+        # RoPE is a torch composition here: always materialized long positions
+        pos = rotary_positions(kv, start_pos, position_ids, T, always=True)
 
         x = _rms1p(hidden, self.input_norm_w, eps)
         q = ops.linear(x, self.q_w).view(B, T, Hq, D).permute(0, 2, 1, 3)
@@ -157,23 +133,10 @@ class Gemma4Block(torch.nn.Module):
                     f"gemma-4 shared-KV layer {self.global_index} requires its "
                     f"donor layer {self.donor} in the same server block range")
 
-        hp = (kv.host_prefix(kv_layer)
-              if hasattr(kv, "host_prefix") else None)
-        if hp is not None:
-            # mixed-device session: the host prefix of the layer whose pools
-            # this block reads (the donor's for shared-KV tail layers).
-            # Sliding layers see only the host suffix still inside the
-            # window; decode-only (backend gates T == 1)
-            attn = ops.attn_paged_mixed(
-                q, kv.k_pages(kv_layer), kv.v_pages(kv_layer),
-                kv.page_table(), start_pos + T, hp[0], hp[1], scale=1.0,
-                window=self.window)
-        else:
-            attn = ops.attn_paged(q, kv.k_pages(kv_layer),
-                                  kv.v_pages(kv_layer), kv.page_table(),
-                                  start_pos.long(), scale=1.0,
-                                  window=self.window)
-        attn = attn.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
+        # the pools (and, in a mixed-device session, the host prefix) of the
+        # layer this block reads: the donor's for shared-KV tail layers
+        attn = paged_attention(q, kv, kv_layer, start_pos, 1.0,
+                               window=self.window)
         a = ops.linear(attn, self.o_w)
         a = _rms1p(a, self.post_attn_norm_w, eps)
         h = hidden + a
@@ -229,6 +192,3 @@ class Gemma4Block(torch.nn.Module):
         m = torch.nn.functional.linear(gact * u, self.down_w)
         m = rms(m, self.post_ffn_norm_w, eps)
         return h + m
-
-    def forward(self, *args, **kw):
-        return self.forward_inference(*args, **kw)

@@ -12,17 +12,16 @@ a flat MI355X-native block:
     ValueHolder grids, no per-layer load/store streams: weights are resident
     in 288 GB HBM by default; the offload tier is a separate module.
 
-Two forward paths (by design, mirroring the reference's split between
-iterate_rpc_inference and run_rpc_forward/backward):
-  forward_inference — HIP kernels + paged KV, no autograd.
-  forward_train     — differentiable eager composition (fp32 softmax) used by
-                      the fine-tuning RPCs; gradients flow to inputs/prompts
-                      only (server weights frozen, ref backend.py:106-109).
+What the block shares with the other families (base class, rotary positions
+and attention dispatch of mixed-device sessions, train-path pieces, 4-bit
+packing) lives in models/block_common.py. The fused-norm chain, the weight
+fold, _lin and the deferred qkv combine are LLaMA-pattern specific and stay
+here; Qwen3 is this block plus the _post_qkv / _post_qkv_train hooks.
 """
 from __future__ import annotations
 
 import math
-from typing import Optional, Tuple
+from typing import Optional
 
 import torch
 import torch.nn.functional as F
@@ -30,44 +29,22 @@ import torch.nn.functional as F
 from bloombee_amd import ops
 from bloombee_amd.kv.paged import SessionHandle
 from bloombee_amd.models.base import ModelConfig
+from bloombee_amd.models.block_common import (  # noqa: F401 (RopeTables: re-export)
+    FamilyBlock, RopeTables, pack_q4, paged_attention_qkv, rms_train,
+    rope_attn_train, rotary_positions, split_heads, swiglu_mlp_train)
 
 
-class RopeTables:
-    """Shared host-precomputed cos/sin tables, materialized per device."""
-
-    def __init__(self, config: ModelConfig):
-        self.config = config
-        cos, sin = ops.rope_cos_sin(
-            config.head_dim, config.max_position_embeddings,
-            theta=config.rope_theta, scaling=config.rope_scaling,
-        )
-        self._cos, self._sin = cos, sin
-        self._cache = {}
-
-    def get(self, device: torch.device):
-        key = str(device)
-        if key not in self._cache:
-            self._cache[key] = (self._cos.to(device), self._sin.to(device))
-        return self._cache[key]
-
-
-class LlamaBlock(torch.nn.Module):
+class LlamaBlock(FamilyBlock):
     def __init__(self, config: ModelConfig, layer_index: int = 0,
                  rope: Optional[RopeTables] = None):
-        super().__init__()
-        self.config = config
-        self.layer_index = layer_index
+        super().__init__(config, layer_index)
         H = config.hidden_size
         D = config.head_dim
         Hq, Hkv = config.num_attention_heads, config.num_key_value_heads
         I = config.intermediate_size
-        dt = config.dtype
         self.Hq, self.Hkv, self.D, self.I = Hq, Hkv, D, I
         self.scale = 1.0 / math.sqrt(D)
-
-        def p(*shape):
-            return torch.nn.Parameter(torch.empty(*shape, dtype=dt), requires_grad=False)
-
+        p = self.p
         self.input_norm_w = p(H)
         self.qkv_w = p((Hq + 2 * Hkv) * D, H)     # fused q|k|v
         self.o_w = p(H, Hq * D)
@@ -85,24 +62,6 @@ class LlamaBlock(torch.nn.Module):
         # int32 buffer, a slice of H/64 entries each for o-proj and down-proj;
         # zero between launches (the kernel resets what it counted)
         self._splitk_cnt = None
-
-    @torch.no_grad()
-    def init_random(self, seed: Optional[int] = None):
-        """Random-init weights. Generates on the parameters' current device —
-        device-side RNG for resident blocks (seconds for 70B-class shards vs
-        minutes of host randn + transfer). Same (device kind, seed) => same
-        weights, which is what the multi-rank parity argument needs."""
-        s = seed if seed is not None else 1234 + self.layer_index
-        dev = self.input_norm_w.device
-        gen = torch.Generator(device=dev).manual_seed(s)
-        std = 0.02 / math.sqrt(2 * self.config.num_hidden_layers)
-        for name, w in self.named_parameters():
-            if name.endswith("norm_w"):
-                w.fill_(1.0)
-            else:
-                w.copy_(torch.randn(w.shape, generator=gen, dtype=torch.float32,
-                                    device=dev).mul_(std).to(w.dtype))
-        return self
 
     def _fuse_norm_gate(self, hidden) -> bool:
         """All four decode GEMMs must hit the v2 kernel (K%256) with
@@ -172,17 +131,7 @@ class LlamaBlock(torch.nn.Module):
         flexgen_utils/compression.py:94-210). keep_full=False drops the
         bf16 weights (4x memory; the block becomes inference-only and
         prefill-shaped GEMMs dequantize on the fly)."""
-        self._w4 = {}
-        for name in ("qkv_w", "o_w", "gate_up_w", "down_w"):
-            w = getattr(self, name).detach()
-            packed, scale, zero = ops.quant4_pack(w)
-            N = w.shape[0]
-            self._w4[name] = (packed.reshape(N, -1).contiguous(),
-                              scale.reshape(N, -1).half().contiguous(),
-                              zero.reshape(N, -1).half().contiguous(), N)
-            if not keep_full:
-                getattr(self, name).data = torch.empty(
-                    0, dtype=w.dtype, device=w.device)
+        pack_q4(self, ("qkv_w", "o_w", "gate_up_w", "down_w"), keep_full)
         return self
 
     def _lin(self, x, w, name, **kw):
@@ -201,6 +150,15 @@ class LlamaBlock(torch.nn.Module):
             if d is not None:
                 y = y + d
         return y
+
+    def _post_qkv(self, qkv: torch.Tensor, B: int, T: int) -> torch.Tensor:
+        """Hook on the combined bf16 QKV buffer (B, T, (Hq+2Hkv)*D) before
+        RoPE; a no-op here. An override turns the deferred qkv combine off."""
+        return qkv
+
+    def _post_qkv_train(self, q: torch.Tensor, k: torch.Tensor):
+        """The train path's form of the hook: q, k as (B, H, T, D)."""
+        return q, k
 
     # ------------------------------------------------------------------
     # inference path (HIP kernels, paged KV)
@@ -232,7 +190,9 @@ class LlamaBlock(torch.nn.Module):
         pb = getattr(self, "prev_block", None)
         # the qkv GEMM's split-K combine folds into rope_kv_write: the GEMM
         # hands over its f32 slabs and the combine launch disappears
-        defer = fuse_norm and ops.fuse_qkv_rope_ok(hidden, self.qkv_w, D)
+        # (a _post_qkv override needs combined values: no deferral then)
+        defer = (fuse_norm and type(self)._post_qkv is LlamaBlock._post_qkv
+                 and ops.fuse_qkv_rope_ok(hidden, self.qkv_w, D))
         if fuse_norm and pb is not None and getattr(pb, "_ss_valid", False):
             # previous block's down-proj left sum-of-squares for `hidden`;
             # norm weight is folded into qkv_w -> invr-only norm (mode 2)
@@ -245,18 +205,13 @@ class LlamaBlock(torch.nn.Module):
         else:
             x = ops.rms_norm(hidden, self.input_norm_w, cfg.rms_norm_eps)
             qkv = self._lin(x, self.qkv_w, "qkv_w")        # (B, T, (Hq+2Hkv)D)
+        if not defer:   # deferral implies the no-op hook
+            qkv = self._post_qkv(qkv, B, T)
         cos, sin = self.rope.get(hidden.device)
         kp = kv.k_pages(self.layer_index)
         vp = kv.v_pages(self.layer_index)
         pt = kv.page_table()
-        # mixed-device sessions (host KV prefix + device recent segment,
-        # kv.swap_in_as_prefix): paged indices are LOCAL to the device pool
-        # but rotary positions must stay ABSOLUTE
-        off = getattr(kv, "pos_offset", 0)
-        if off and position_ids is None:
-            position_ids = (start_pos.view(B, 1) + off
-                            + torch.arange(T, device=hidden.device)
-                            .view(1, T)).int()
+        position_ids = rotary_positions(kv, start_pos, position_ids, T)
         # fused RoPE + paged KV write on the raw GEMM output, then attention
         # reads q in place and emits the O-projection input — no transposes
         ctx_lens = None   # start_pos + T, a by-product of the fused launch
@@ -269,30 +224,9 @@ class LlamaBlock(torch.nn.Module):
         else:
             ops.rope_kv_write_(qkv, Hq, Hkv, cos, sin, position_ids, kp, vp,
                                pt, start_pos)
-        hp = (kv.host_prefix(self.layer_index)
-              if hasattr(kv, "host_prefix") else None)
-        if hp is not None:
-            # exact two-segment merge (ref _mixed_device_attention): the
-            # host prefix is attended on the CPU, the recent segment via
-            # the paged pool; decode-only (backend gates T == 1)
-            D_ = self.D
-            q = (qkv[..., : Hq * D_].view(B, T, Hq, D_)
-                 .permute(0, 2, 1, 3).contiguous())
-            attn = ops.attn_paged_mixed(q, kp, vp, pt, start_pos + T,
-                                        hp[0], hp[1], self.scale)
-            attn = attn.permute(0, 2, 1, 3).reshape(B, T, Hq * D_)
-        elif tree_mask is not None:
-            # tree-structured verify step (spec decoding): unfused q view +
-            # the tree-mask attention path
-            q = (qkv[..., : Hq * D].view(B, T, Hq, D)
-                 .permute(0, 2, 1, 3).contiguous())
-            attn = ops.attn_paged(q, kp, vp, pt, start_pos.long(), self.scale,
-                                  tree_mask=tree_mask)
-            attn = attn.permute(0, 2, 1, 3).reshape(B, T, Hq * D)
-        else:
-            attn = ops.attn_paged_qkv(qkv, Hq, Hkv, kp, vp, pt, start_pos,
-                                      self.scale,
-                                      ctx_lens=ctx_lens if T == 1 else None)
+        attn = paged_attention_qkv(qkv, kv, self.layer_index, start_pos, Hq,
+                                   Hkv, self.scale, tree_mask=tree_mask,
+                                   ctx_lens=ctx_lens)
         if fuse_norm:
             # h2 = hidden + o(attn) via the GEMM's residual epilogue, which
             # also emits row sum-of-squares; the post-attention rmsnorm
@@ -330,14 +264,7 @@ class LlamaBlock(torch.nn.Module):
     # training path (differentiable; full sequence, no KV cache)
     # ------------------------------------------------------------------
     def forward_train(self, hidden: torch.Tensor, start_pos: int = 0) -> torch.Tensor:
-        B, T, H = hidden.shape
-        Hq, Hkv, D = self.Hq, self.Hkv, self.D
-        cfg = self.config
-
-        def rms(x, w):
-            xf = x.float()
-            return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + cfg.rms_norm_eps)
-                    ).to(x.dtype) * w
+        eps = self.config.rms_norm_eps
 
         def lin(x_, w, name):
             # training path honors active LoRA adapters too (the inference
@@ -350,29 +277,11 @@ class LlamaBlock(torch.nn.Module):
                     y = y + d
             return y
 
-        x = rms(hidden, self.input_norm_w)
-        qkv = lin(x, self.qkv_w, "qkv_w").view(B, T, Hq + 2 * Hkv, D).permute(0, 2, 1, 3)
-        q, k, v = qkv.split([Hq, Hkv, Hkv], dim=1)
-        cos, sin = self.rope.get(hidden.device)
-        pos = torch.arange(start_pos, start_pos + T, device=hidden.device)
-        c = cos[pos].view(1, 1, T, D // 2).float()
-        s = sin[pos].view(1, 1, T, D // 2).float()
-
-        def rot(t):
-            tf = t.float()
-            t1, t2 = tf[..., : D // 2], tf[..., D // 2:]
-            return torch.cat([t1 * c - t2 * s, t2 * c + t1 * s], -1).to(t.dtype)
-
-        q, k = rot(q), rot(k)
-        attn = ops.attn_train(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3),
-                              v.permute(0, 2, 1, 3), self.scale)
-        attn = attn.reshape(B, T, Hq * D)
+        x = rms_train(hidden, self.input_norm_w, eps)
+        q, k, v = split_heads(lin(x, self.qkv_w, "qkv_w"), self.Hq, self.Hkv,
+                              self.D)
+        q, k = self._post_qkv_train(q, k)
+        attn = rope_attn_train(q, k, v, self.rope, start_pos, self.scale)
         h2 = hidden + lin(attn, self.o_w, "o_w")
-        y = rms(h2, self.post_norm_w)
-        gu = F.linear(y, self.gate_up_w)
-        g, u = gu.split([self.I, self.I], dim=-1)
-        m = F.linear(F.silu(g.float()).to(u.dtype) * u, self.down_w)
-        return h2 + m
-
-    def forward(self, *args, **kw):
-        return self.forward_inference(*args, **kw)
+        y = rms_train(h2, self.post_norm_w, eps)
+        return h2 + swiglu_mlp_train(y, self.gate_up_w, self.down_w)

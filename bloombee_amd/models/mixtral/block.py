@@ -16,30 +16,25 @@ import torch
 from bloombee_amd import ops
 from bloombee_amd.kv.paged import SessionHandle
 from bloombee_amd.models.base import ModelConfig
-from bloombee_amd.models.llama.block import RopeTables
+from bloombee_amd.models.block_common import (
+    FamilyBlock, RopeTables, pack_q4, paged_attention_qkv, rms_train,
+    rope_attn_train, rotary_positions, split_heads, swiglu_mlp_train)
 
 
-class MixtralBlock(torch.nn.Module):
+class MixtralBlock(FamilyBlock):
     def __init__(self, config: ModelConfig, layer_index: int = 0,
                  rope: Optional[RopeTables] = None):
-        super().__init__()
-        self.config = config
-        self.layer_index = layer_index
+        super().__init__(config, layer_index)
         H = config.hidden_size
         D = config.head_dim
         Hq, Hkv = config.num_attention_heads, config.num_key_value_heads
         I = config.intermediate_size
         E = int(config.extras.get("num_local_experts", 8))
         K = int(config.extras.get("num_experts_per_tok", 2))
-        dt = config.dtype
         self.Hq, self.Hkv, self.D, self.I, self.E, self.topk = Hq, Hkv, D, I, E, K
         self.scale = 1.0 / math.sqrt(D)
         self.rope = rope if rope is not None else RopeTables(config)
-
-        def p(*shape):
-            return torch.nn.Parameter(torch.empty(*shape, dtype=dt),
-                                      requires_grad=False)
-
+        p = self.p
         self.input_norm_w = p(H)
         self.qkv_w = p((Hq + 2 * Hkv) * D, H)
         self.o_w = p(H, Hq * D)
@@ -47,20 +42,6 @@ class MixtralBlock(torch.nn.Module):
         self.router_w = p(E, H)
         self.expert_gate_up_w = p(E, 2 * I, H)
         self.expert_down_w = p(E, H, I)
-
-    @torch.no_grad()
-    def init_random(self, seed: Optional[int] = None):
-        s = seed if seed is not None else 1234 + self.layer_index
-        dev = self.input_norm_w.device
-        gen = torch.Generator(device=dev).manual_seed(s)
-        std = 0.02 / math.sqrt(2 * self.config.num_hidden_layers)
-        for name, w in self.named_parameters():
-            if name.endswith("norm_w"):
-                w.fill_(1.0)
-            else:
-                w.copy_(torch.randn(w.shape, generator=gen, dtype=torch.float32,
-                                    device=dev).mul_(std).to(w.dtype))
-        return self
 
     # -- 4-bit weights ----------------------------------------------------
     @torch.no_grad()
@@ -71,18 +52,8 @@ class MixtralBlock(torch.nn.Module):
         bytes: the attention projections through ops.linear_w4, the grouped
         expert GEMMs through ops.moe_gemm_grouped_w4. keep_full=False drops
         the bf16 weights (the block becomes inference-only)."""
-        self._w4 = {}
-        for name in ("qkv_w", "o_w", "expert_gate_up_w", "expert_down_w"):
-            w = getattr(self, name).detach()
-            packed, scale, zero = ops.quant4_pack(w)
-            lead = tuple(w.shape[:-1])
-            self._w4[name] = (packed.reshape(*lead, -1).contiguous(),
-                              scale.reshape(*lead, -1).half().contiguous(),
-                              zero.reshape(*lead, -1).half().contiguous(),
-                              w.shape[-2])
-            if not keep_full:
-                getattr(self, name).data = torch.empty(
-                    0, dtype=w.dtype, device=w.device)
+        pack_q4(self, ("qkv_w", "o_w", "expert_gate_up_w", "expert_down_w"),
+                keep_full)
         return self
 
     def _lin(self, x, w, name):
@@ -176,36 +147,21 @@ class MixtralBlock(torch.nn.Module):
 
     @torch.no_grad()
     def forward_inference(self, hidden: torch.Tensor, kv: SessionHandle,
-                          start_pos: torch.Tensor,
-                          position_ids=None) -> torch.Tensor:
+                          start_pos: torch.Tensor, position_ids=None,
+                          tree_mask=None) -> torch.Tensor:
         B, T, H = hidden.shape
         Hq, Hkv = self.Hq, self.Hkv
         cfg = self.config
         x = ops.rms_norm(hidden, self.input_norm_w, cfg.rms_norm_eps)
         qkv = self._lin(x, self.qkv_w, "qkv_w")
         cos, sin = self.rope.get(hidden.device)
-        kp = kv.k_pages(self.layer_index)
-        vp = kv.v_pages(self.layer_index)
-        pt = kv.page_table()
-        # mixed-device sessions (host KV prefix + device recent segment):
-        # pool positions are local, rotary stays absolute (see llama block)
-        off = getattr(kv, "pos_offset", 0)
-        if off and position_ids is None:
-            position_ids = (start_pos.view(B, 1) + off
-                            + torch.arange(T, device=hidden.device)
-                            .view(1, T)).int()
-        ops.rope_kv_write_(qkv, Hq, Hkv, cos, sin, position_ids, kp, vp, pt,
+        ops.rope_kv_write_(qkv, Hq, Hkv, cos, sin,
+                           rotary_positions(kv, start_pos, position_ids, T),
+                           kv.k_pages(self.layer_index),
+                           kv.v_pages(self.layer_index), kv.page_table(),
                            start_pos)
-        hp = (kv.host_prefix(self.layer_index)
-              if hasattr(kv, "host_prefix") else None)
-        if hp is not None:
-            # exact two-segment merge; decode-only (backend gates T == 1)
-            attn = ops.attn_paged_mixed_qkv(qkv, Hq, Hkv, kp, vp, pt,
-                                            start_pos + T, hp[0], hp[1],
-                                            self.scale)
-        else:
-            attn = ops.attn_paged_qkv(qkv, Hq, Hkv, kp, vp, pt, start_pos,
-                                      self.scale)
+        attn = paged_attention_qkv(qkv, kv, self.layer_index, start_pos, Hq,
+                                   Hkv, self.scale, tree_mask=tree_mask)
         a = self._lin(attn, self.o_w, "o_w")
         h2, y = ops.rms_norm_residual(a, hidden, self.post_norm_w, cfg.rms_norm_eps)
         return h2 + self._moe(y)
@@ -217,28 +173,13 @@ class MixtralBlock(torch.nn.Module):
                 "quantized with quantize_weights_q4(keep_full=False) and is "
                 "inference-only")
         B, T, H = hidden.shape
-        Hq, Hkv, D = self.Hq, self.Hkv, self.D
-        cfg = self.config
-
-        def rms(x, w):
-            xf = x.float()
-            return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True)
-                                     + cfg.rms_norm_eps)).to(x.dtype) * w
-
-        x = rms(hidden, self.input_norm_w)
-        qkv = torch.nn.functional.linear(x, self.qkv_w)
-        qkv = qkv.view(B, T, Hq + 2 * Hkv, D).permute(0, 2, 1, 3)
-        q, k, v = qkv.split([Hq, Hkv, Hkv], dim=1)
-        cos, sin = self.rope.get(hidden.device)
-        pos = torch.arange(start_pos, start_pos + T,
-                           device=hidden.device).view(1, T).expand(B, T)
-        from bloombee_amd.ops import reference as refops
-        q, k = refops.rope_apply(q, k, cos, sin, pos)
-        attn = ops.attn_train(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3),
-                              v.permute(0, 2, 1, 3), self.scale)
-        attn = attn.reshape(B, T, Hq * D)
+        eps = self.config.rms_norm_eps
+        x = rms_train(hidden, self.input_norm_w, eps)
+        q, k, v = split_heads(torch.nn.functional.linear(x, self.qkv_w),
+                              self.Hq, self.Hkv, self.D)
+        attn = rope_attn_train(q, k, v, self.rope, start_pos, self.scale)
         h2 = hidden + torch.nn.functional.linear(attn, self.o_w)
-        y = rms(h2, self.post_norm_w)
+        y = rms_train(h2, self.post_norm_w, eps)
 
         flat = y.reshape(-1, H)
         logits = torch.nn.functional.linear(flat, self.router_w).float()
@@ -252,17 +193,11 @@ class MixtralBlock(torch.nn.Module):
             if rows.numel() == 0:
                 continue
             xe = flat[rows]
-            gu = torch.nn.functional.linear(xe, self.expert_gate_up_w[le])
-            g, u = gu.split([self.I, self.I], dim=-1)
-            h = torch.nn.functional.linear(
-                torch.nn.functional.silu(g.float()).to(u.dtype) * u,
-                self.expert_down_w[le])
+            h = swiglu_mlp_train(xe, self.expert_gate_up_w[le],
+                                 self.expert_down_w[le])
             w = (weights * sel.to(weights.dtype)).sum(-1)[rows]
             out = out.index_add(0, rows, h * w.unsqueeze(-1))
         if getattr(self, "ep_enabled", False):
             from bloombee_amd.parallel.expert import ep_all_reduce
             ep_all_reduce(out, self.ep_group)
         return h2 + out.view(B, T, H)
-
-    def forward(self, *args, **kw):
-        return self.forward_inference(*args, **kw)

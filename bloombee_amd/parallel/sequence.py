@@ -157,6 +157,7 @@ def cp_prefill_llama(stack, kv_handle, hidden_shard: torch.Tensor,
     import torch.nn.functional as F
 
     from bloombee_amd import ops
+    from bloombee_amd.models.block_common import rms_train
     from bloombee_amd.ops import reference as refops
 
     cfg = stack.config
@@ -164,26 +165,22 @@ def cp_prefill_llama(stack, kv_handle, hidden_shard: torch.Tensor,
     dev = hidden_shard.device
     hidden = hidden_shard
 
-    def rms(x, w):
-        xf = x.float()
-        return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True)
-                                 + cfg.rms_norm_eps)).to(x.dtype) * w
-
+    eps = cfg.rms_norm_eps
     for blk in stack.blocks:
         if not (hasattr(blk, "qkv_w") and hasattr(blk, "gate_up_w")):
             raise NotImplementedError(
                 "cp_prefill_llama supports llama-pattern blocks")
         Hq, Hkv, D = blk.Hq, blk.Hkv, blk.D
         G = Hq // Hkv
-        x = rms(hidden, blk.input_norm_w)
+        x = rms_train(hidden, blk.input_norm_w, eps)
         qkv = (F.linear(x, blk.qkv_w).view(B, T_loc, Hq + 2 * Hkv, D)
                .permute(0, 2, 1, 3))
         q, k, v = qkv.split([Hq, Hkv, Hkv], dim=1)
         if hasattr(blk, "q_norm_w"):
-            # qwen3-pattern: per-head RMS on raw q/k before RoPE (the rms
-            # helper normalizes over the last dim = D, weight (D,))
-            q = rms(q, blk.q_norm_w)
-            k = rms(k, blk.k_norm_w)
+            # qwen3-pattern: per-head RMS on raw q/k before RoPE (rms_train
+            # normalizes over the last dim = D, weight (D,))
+            q = rms_train(q, blk.q_norm_w, eps)
+            k = rms_train(k, blk.k_norm_w, eps)
         cos, sin = blk.rope.get(dev)
         pos = (torch.arange(rank * T_loc, (rank + 1) * T_loc, device=dev)
                .view(1, T_loc).expand(B, T_loc))
@@ -217,7 +214,7 @@ def cp_prefill_llama(stack, kv_handle, hidden_shard: torch.Tensor,
                 .permute(0, 2, 1, 3).reshape(B, T_loc, Hq * D))
 
         h2 = hidden + F.linear(attn, blk.o_w)
-        y = rms(h2, blk.post_norm_w)
+        y = rms_train(h2, blk.post_norm_w, eps)
         gu = F.linear(y, blk.gate_up_w)
         g, u = gu.split([gu.shape[-1] // 2] * 2, dim=-1)
         hidden = h2 + F.linear(

@@ -9,7 +9,8 @@ falcon-tiny emit the same token at every step either way).
 """
 import torch
 
-FAMILIES = ["bloom-tiny", "falcon-tiny", "mixtral-tiny", "gemma4-tiny"]
+FAMILIES = ["bloom-tiny", "falcon-tiny", "mixtral-tiny", "gemma4-tiny",
+            "llama-tiny", "qwen3-tiny"]
 
 BATCH, PROMPT, STEPS = 2, 40, 12
 

@@ -3,7 +3,7 @@
   1. SwiGLU in the gate_up GEMM (gemm_skinny_swiglu)   vs gemm_skinny + swiglu
   2. qkv split-K slabs into rope_kv_write_part         vs combine + rope_kv_write_
   3. in-launch split-K reduce (gemm_skinny cnt=...)    vs GEMM + combine launch
-  4. a two-block llama stack, all switches on          vs all off
+  4. a two-block llama / qwen3 stack, all switches on  vs all off
 
 Every comparison with the unfused path is `torch.equal`: the fused kernels
 round at the same places and sum in the same order. Exact-arithmetic data
@@ -292,16 +292,24 @@ def test_inlaunch_reduce_graph_replay():
 # 4. block level: all switches on vs all off
 # ---------------------------------------------------------------------------
 
-def _run_stack(cfg, B, x_pre, x_dec, on, monkeypatch):
+def _run_stack(cfg, B, x_pre, x_dec, on, monkeypatch, block_cls=None):
     from bloombee_amd.kv import PagedKVCache
     from bloombee_amd.models.llama.block import LlamaBlock, RopeTables
+
+    block_cls = block_cls or LlamaBlock
 
     monkeypatch.setattr(iface, "_FUSE_SWIGLU", on)
     monkeypatch.setattr(iface, "_FUSE_QKV_ROPE", on)
     monkeypatch.setattr(iface, "_INLAUNCH_COMBINE",
                         frozenset(("o", "down")) if on else frozenset())
     rope = RopeTables(cfg)
-    blocks = [LlamaBlock(cfg, i, rope).init_random(40 + i).to(DEV) for i in range(2)]
+    blocks = [block_cls(cfg, i, rope).init_random(40 + i).to(DEV) for i in range(2)]
+    gen = torch.Generator().manual_seed(77)
+    for blk in blocks:      # qwen3: non-unit per-head norm weights
+        for name in ("q_norm_w", "k_norm_w"):
+            if hasattr(blk, name):
+                w = getattr(blk, name)
+                w.data.copy_((1 + 0.3 * torch.randn(w.shape, generator=gen)).to(BF))
     object.__setattr__(blocks[1], "prev_block", blocks[0])
     pool = PagedKVCache(2, cfg.num_key_value_heads, cfg.head_dim, max_tokens=4096,
                         device=DEV, dtype=BF)
@@ -322,6 +330,32 @@ def _run_stack(cfg, B, x_pre, x_dec, on, monkeypatch):
     return outs, pages
 
 
+def _stack_cfg(shape):
+    from bloombee_amd.models.base import ModelConfig
+
+    if shape == "h256":
+        return ModelConfig(hidden_size=256, num_hidden_layers=2, num_attention_heads=4,
+                           num_key_value_heads=2, head_dim=64, intermediate_size=512,
+                           max_position_embeddings=128)
+    return ModelConfig(hidden_size=1024, num_hidden_layers=2, num_attention_heads=8,
+                       num_key_value_heads=2, head_dim=128, intermediate_size=1024,
+                       max_position_embeddings=128)
+
+
+def _check_on_vs_off(shape, B, monkeypatch, block_cls=None):
+    cfg = _stack_cfg(shape)
+    gen = torch.Generator().manual_seed(B)
+    x_pre = _randn_bf(gen, B, 5, cfg.hidden_size).to(DEV)
+    x_dec = [_randn_bf(gen, B, 1, cfg.hidden_size).to(DEV) for _ in range(3)]
+    off, pages_off = _run_stack(cfg, B, x_pre, x_dec, False, monkeypatch, block_cls)
+    on, pages_on = _run_stack(cfg, B, x_pre, x_dec, True, monkeypatch, block_cls)
+    for i, (a, b) in enumerate(zip(on, off)):
+        assert_same(a, b, f"step {i} output")
+    for i, ((k1, v1), (k0, v0)) in enumerate(zip(pages_on, pages_off)):
+        assert_same(k1, k0, f"layer {i} k_pages")
+        assert_same(v1, v0, f"layer {i} v_pages")
+
+
 @pytest.mark.parametrize("B", [1, 17, 32])
 @pytest.mark.parametrize("shape", ["h256", "h1024-splitk"])
 def test_block_switches_on_vs_off(shape, B, monkeypatch):
@@ -332,23 +366,16 @@ def test_block_switches_on_vs_off(shape, B, monkeypatch):
     There the plain gate_up GEMM splits K as well, so linear_swiglu keeps
     the separate kernels (fuse_swiglu_ok: a never-splitting fused kernel
     would order the sums differently)."""
-    from bloombee_amd.models.base import ModelConfig
+    _check_on_vs_off(shape, B, monkeypatch)
 
-    if shape == "h256":
-        cfg = ModelConfig(hidden_size=256, num_hidden_layers=2, num_attention_heads=4,
-                          num_key_value_heads=2, head_dim=64, intermediate_size=512,
-                          max_position_embeddings=128)
-    else:
-        cfg = ModelConfig(hidden_size=1024, num_hidden_layers=2, num_attention_heads=8,
-                          num_key_value_heads=2, head_dim=128, intermediate_size=1024,
-                          max_position_embeddings=128)
-    gen = torch.Generator().manual_seed(B)
-    x_pre = _randn_bf(gen, B, 5, cfg.hidden_size).to(DEV)
-    x_dec = [_randn_bf(gen, B, 1, cfg.hidden_size).to(DEV) for _ in range(3)]
-    off, pages_off = _run_stack(cfg, B, x_pre, x_dec, False, monkeypatch)
-    on, pages_on = _run_stack(cfg, B, x_pre, x_dec, True, monkeypatch)
-    for i, (a, b) in enumerate(zip(on, off)):
-        assert_same(a, b, f"step {i} output")
-    for i, ((k1, v1), (k0, v0)) in enumerate(zip(pages_on, pages_off)):
-        assert_same(k1, k0, f"layer {i} k_pages")
-        assert_same(v1, v0, f"layer {i} v_pages")
+
+@pytest.mark.parametrize("B", [1, 32])
+@pytest.mark.parametrize("shape", ["h256", "h1024-splitk"])
+def test_qwen3_block_switches_on_vs_off(shape, B, monkeypatch):
+    """The same for two chained Qwen3 blocks with random non-unit q_norm_w /
+    k_norm_w. Qwen3 is the LLaMA block plus the _post_qkv hook, so it takes
+    the SwiGLU epilogue and the in-launch o / down combine; the hook needs
+    combined QKV values, so the deferred qkv combine stays off for it."""
+    from bloombee_amd.models.qwen3.block import Qwen3Block
+
+    _check_on_vs_off(shape, B, monkeypatch, Qwen3Block)

@@ -207,9 +207,7 @@ def test_mixed_composition_switch(monkeypatch):
     check(case, want, 0, "composition")
 
 
-# llama and qwen3 had the host-prefix branch before; on the GPU their mixed
-# steps now take the kernel path too
-@pytest.mark.parametrize("model", FAMILIES + ["llama-tiny", "qwen3-tiny"])
+@pytest.mark.parametrize("model", FAMILIES)
 def test_mixed_device_decode_family_gpu(model):
     """Host-prefixed decode on the GPU is as close to the CPU reference run
     as the never-swapped GPU run: e_mixed <= 2 * e_dense + 2**-8 * max|dense|

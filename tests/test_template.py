@@ -33,3 +33,26 @@ def test_generated_family_decodes(tmp_path):
         assert torch.equal(full, tok)
     finally:
         sys.path.remove(str(tmp_path))
+
+
+def test_generated_family_mixed_device(tmp_path):
+    """A generated family handles mixed-device sessions: decode hidden states
+    with the committed KV moved to a host prefix match the never-swapped
+    run's. Before the generated block went through block_common's
+    rotary_positions / paged_attention_qkv it ignored the host prefix and
+    this comparison failed (max|diff| 0.0725 at max|dense| 0.0771)."""
+    from bloombee_amd.models.template import generate_family
+    from mixed_device_scenario import decode_hidden, make_engine
+    from test_mixed_device_families import assert_hidden_match
+
+    generate_family(
+        "bloombee_amd/models/template/spec_llama.yaml", str(tmp_path))
+    sys.path.insert(0, str(tmp_path))
+    try:
+        importlib.import_module("myllama")
+        eng = make_engine("myllama-tiny")
+        dense = decode_hidden(eng, swapped=False)
+        mixed = decode_hidden(eng, swapped=True)
+        assert_hidden_match(dense, mixed)
+    finally:
+        sys.path.remove(str(tmp_path))
