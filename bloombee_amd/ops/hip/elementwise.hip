@@ -237,58 +237,20 @@ __global__ void add_kernel(const unsigned short* __restrict__ a,
 // v heads: straight copy -> v_pages. One launch replaces rope + kv_write and
 // removes every transpose copy between the QKV GEMM and attention.
 // grid: (B*T, Hq+2Hkv), block: 64.
-//
-// PART: the source is the QKV GEMM's split-K output before its combine, f32
-// slabs (ksplit, B*T, (Hq+2Hkv)*D) plus an optional bias. Each element is the
-// slabs summed in split order, then the bias, rounded once to bf16 — what
-// gemm_skinny_combine_ss_kernel would have stored — and the same rotary and
-// page-write code runs on that value, so the combine launch and the bf16
-// round trip between the two kernels disappear. Rotated q goes to the bf16
-// qkv buffer; the k and v sections of that buffer are never written. Slabs
-// are read 16 B per lane (V = 4 elements), D % 8 == 0.
 // ---------------------------------------------------------------------------
 
-template <bool PART>
 __global__ void rope_kv_write_kernel(
-    unsigned short* __restrict__ qkv, const float* __restrict__ part,
-    const unsigned short* __restrict__ bias, int ksplit,
-    const float* __restrict__ cos_t,
+    unsigned short* __restrict__ qkv, const float* __restrict__ cos_t,
     const float* __restrict__ sin_t, const int* __restrict__ pos,
     unsigned short* __restrict__ k_pages, unsigned short* __restrict__ v_pages,
     const int* __restrict__ page_table, const int* __restrict__ start_pos,
-    int B, int Hq, int Hkv, int T, int D, int P, int maxp, int max_pos,
-    int* __restrict__ ctx_out = nullptr) {  // (B,) start_pos + T, or null
-  constexpr int V = PART ? 4 : 1;   // consecutive elements per lane
+    int B, int Hq, int Hkv, int T, int D, int P, int maxp, int max_pos) {
   const int bt = blockIdx.x;
   const int b = bt / T, t = bt % T;
   const int h = blockIdx.y;
-  // the context lengths attention needs next (every layer used to launch an
-  // elementwise start_pos + 1 for them): one lane per row writes them here
-  if (ctx_out && h == 0 && t == 0 && threadIdx.x == 0)
-    ctx_out[b] = start_pos[b] + T;
   const int X = Hq + 2 * Hkv;
   const long hoff = (((long)b * T + t) * X + h) * D;
   unsigned short* base = qkv + hoff;
-  // V source elements at head offset i, as the bf16-rounded f32 values
-  auto load = [&](int i, float* x) {
-    if constexpr (PART) {
-      const long total = (long)B * T * X * D;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      for (int s = 0; s < ksplit; ++s) {
-        const f32x4 p =
-            *reinterpret_cast<const f32x4*>(part + s * total + hoff + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += p[e];
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (bias) v[e] += bf2f(bias[h * D + i + e]);
-        x[e] = bf2f(f2bf(v[e]));
-      }
-    } else {
-      x[0] = bf2f(base[i]);
-    }
-  };
 
   const int abspos = start_pos[b] + t;
   if (h >= Hq + Hkv) {  // v head: copy to pages (d-major V layout: transpose
@@ -296,16 +258,7 @@ __global__ void rope_kv_write_kernel(
     const int page = page_table[b * maxp + abspos / P];
     const int slot = abspos % P;
     unsigned short* dst = v_pages + ((long)page * Hkv + hv) * D * P + slot;
-    for (int i = threadIdx.x * V; i < D; i += blockDim.x * V) {
-      if constexpr (PART) {
-        float x[V];
-        load(i, x);
-#pragma unroll
-        for (int e = 0; e < V; ++e) dst[(long)(i + e) * P] = f2bf(x[e]);
-      } else {
-        dst[(long)i * P] = base[i];
-      }
-    }
+    for (int i = threadIdx.x; i < D; i += blockDim.x) dst[(long)i * P] = base[i];
     return;
   }
   const int p = min(max(pos ? pos[b * T + t] : abspos, 0), max_pos - 1);
@@ -317,31 +270,125 @@ __global__ void rope_kv_write_kernel(
     const int page = page_table[b * maxp + abspos / P];
     dst = k_pages + (((long)page * Hkv + hk) * P + (abspos % P)) * D;
   }
-  for (int i = threadIdx.x * V; i < D / 2; i += blockDim.x * V) {
-    float xa[V], xb[V];
-    load(i, xa);
-    load(i + D / 2, xb);
-    unsigned short oa[V], ob[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      // both instantiations must round alike: two products, then the
-      // sum, each rounded (what the bf16-source kernel has always
-      // compiled to); left to itself the compiler fuses the PART form
-      // into fma and the q/k bits drift by an ulp
+  for (int i = threadIdx.x; i < D / 2; i += blockDim.x) {
+    // this kernel and rope_kv_write_part_kernel must round alike: two
+    // products, then the sum, each rounded (what this kernel has always
+    // compiled to); left to itself the compiler fuses the slab-source form
+    // into fma and the q/k bits drift by an ulp
 #pragma clang fp contract(off)
-      float x1 = xa[e], x2 = xb[e];
-      float cc = c[i + e], ss = s[i + e];
-      oa[e] = f2bf(x1 * cc - x2 * ss);
-      ob[e] = f2bf(x2 * cc + x1 * ss);
+    float x1 = bf2f(base[i]), x2 = bf2f(base[i + D / 2]);
+    float cc = c[i], ss = s[i];
+    dst[i] = f2bf(x1 * cc - x2 * ss);
+    dst[i + D / 2] = f2bf(x2 * cc + x1 * ss);
+  }
+}
+
+// The same on the QKV GEMM's split-K output before its combine: f32 slabs
+// (ksplit, B*T, (Hq+2Hkv)*D) plus an optional bias. Each element is the slabs
+// summed in split order, then the bias, rounded once to bf16 — what
+// gemm_skinny_combine_ss_kernel would have stored — and the same rotary and
+// page-write arithmetic runs on that value, so the combine launch and the
+// bf16 round trip between the two kernels disappear. Rotated q goes to the
+// bf16 qkv buffer; the k and v sections of that buffer are never written.
+//
+// grid: (B*T, ceil((Hq+2Hkv)*D/8 / 256)), block: 256. A lane owns one item
+// of its (b, t) row: head h = item / (D/8) and the two 16 B groups at head
+// offsets i = 4 * (item % (D/8)) and i + D/2, the rotary partners (a v head
+// copies both). Every lane of every wave but the row's last partial block
+// works, and a lane requests all its slab pieces — 2 * min(ksplit, 8) loads,
+// the index clamped so none is conditional — before the first add.
+// D % 8 == 0. ctx_out: (B,) start_pos + T, the context lengths attention
+// takes next, written once per batch row.
+__global__ __launch_bounds__(256) void rope_kv_write_part_kernel(
+    unsigned short* __restrict__ qkv, const float* __restrict__ part,
+    const unsigned short* __restrict__ bias, int ksplit,
+    const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+    const int* __restrict__ pos, unsigned short* __restrict__ k_pages,
+    unsigned short* __restrict__ v_pages, const int* __restrict__ page_table,
+    const int* __restrict__ start_pos, int B, int Hq, int Hkv, int T, int D,
+    int P, int maxp, int max_pos, int* __restrict__ ctx_out) {
+  constexpr int NS = 8;             // slabs requested at once
+  const int bt = blockIdx.x;
+  const int b = bt / T, t = bt % T;
+  if (blockIdx.y == 0 && t == 0 && threadIdx.x == 0)
+    ctx_out[b] = start_pos[b] + T;
+  const int X = Hq + 2 * Hkv;
+  const int item = blockIdx.y * blockDim.x + threadIdx.x;
+  if (item >= X * (D / 8)) return;
+  const int h = item / (D / 8);
+  const int i = (item % (D / 8)) * 4;
+  const long total = (long)B * T * X * D;
+  const long hoff = ((long)bt * X + h) * D;
+
+  // slabs in split order from zero, then the bias, one bf16 rounding
+  f32x4 pa[NS], pb[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const float* src = part + min(s, ksplit - 1) * total + hoff + i;
+    pa[s] = *reinterpret_cast<const f32x4*>(src);
+    pb[s] = *reinterpret_cast<const f32x4*>(src + D / 2);
+  }
+  f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+    if (s < ksplit) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        va[e] += pa[s][e];
+        vb[e] += pb[s][e];
+      }
     }
-    if constexpr (PART) {   // 8 B stores
-      *reinterpret_cast<short4v*>(dst + i) =
-          (short4v){(short)oa[0], (short)oa[1], (short)oa[2], (short)oa[3]};
-      *reinterpret_cast<short4v*>(dst + i + D / 2) =
-          (short4v){(short)ob[0], (short)ob[1], (short)ob[2], (short)ob[3]};
-    } else {
-      dst[i] = oa[0];
-      dst[i + D / 2] = ob[0];
+  for (int s = NS; s < ksplit; ++s) {
+    const float* src = part + s * total + hoff + i;
+    const f32x4 qa = *reinterpret_cast<const f32x4*>(src);
+    const f32x4 qb = *reinterpret_cast<const f32x4*>(src + D / 2);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      va[e] += qa[e];
+      vb[e] += qb[e];
     }
   }
+  unsigned short ra[4], rb[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (bias) {
+      va[e] += bf2f(bias[h * D + i + e]);
+      vb[e] += bf2f(bias[h * D + i + D / 2 + e]);
+    }
+    ra[e] = f2bf(va[e]);
+    rb[e] = f2bf(vb[e]);
+  }
+
+  const int abspos = start_pos[b] + t;
+  if (h >= Hq + Hkv) {  // v head: d-major pages, scattered 2 B stores
+    const int hv = h - Hq - Hkv;
+    const int page = page_table[b * maxp + abspos / P];
+    unsigned short* dst = v_pages + ((long)page * Hkv + hv) * D * P + abspos % P;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      dst[(long)(i + e) * P] = ra[e];
+      dst[(long)(i + D / 2 + e) * P] = rb[e];
+    }
+    return;
+  }
+  const int p = min(max(pos ? pos[b * T + t] : abspos, 0), max_pos - 1);
+  const float* c = cos_t + (long)p * (D / 2);
+  const float* s = sin_t + (long)p * (D / 2);
+  unsigned short* dst = qkv + hoff;
+  if (h >= Hq) {  // k head: rotated values go to the pages only
+    const int page = page_table[b * maxp + abspos / P];
+    dst = k_pages + (((long)page * Hkv + (h - Hq)) * P + (abspos % P)) * D;
+  }
+  short4v oa, ob;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    // see rope_kv_write_kernel: products and sum each rounded, no fma
+#pragma clang fp contract(off)
+    float x1 = bf2f(ra[e]), x2 = bf2f(rb[e]);
+    float cc = c[i + e], ss = s[i + e];
+    oa[e] = (short)f2bf(x1 * cc - x2 * ss);
+    ob[e] = (short)f2bf(x2 * cc + x1 * ss);
+  }
+  *reinterpret_cast<short4v*>(dst + i) = oa;
+  *reinterpret_cast<short4v*>(dst + i + D / 2) = ob;
 }

@@ -202,6 +202,39 @@ static SkinnyPlan skinny_plan(long N, long K, long ksplit_req) {
   return {s.ksplit, s.kchunk, true};
 }
 
+// W register sets gemm_skinny_v2_kernel keeps requested per wave (its DEPTH):
+// a set is 4 KB per wave and DEPTH - 1 of them are outstanding at a wait.
+// req > 0 pins a depth for one call, BBAMD_GEMM_WRING for the process.
+// Unset, every shape runs depth 2, the kernel as it was before the ring: in
+// the flagship's kernel trace depth 4 beat it for no shape (gate_up and
+// o/down 3-4 % slower, qkv level; profiles/r06_gemm_wring.md), although it
+// puts 84-144 KB per CU in flight where depth 2 has 28-48 KB, so there is no
+// occupancy or stream-length rule to apply yet.
+static constexpr int kWringDepths[] = {2, 4};
+
+static int skinny_wring(long req) {
+  static const int env = [] {
+    const char* e = std::getenv("BBAMD_GEMM_WRING");
+    return e ? std::atoi(e) : 0;
+  }();
+  if (req <= 0) req = env;
+  if (req <= 0) return 2;
+  TORCH_CHECK(std::find(std::begin(kWringDepths), std::end(kWringDepths), req) !=
+                  std::end(kWringDepths),
+              "gemm_skinny W ring depth must be 2 or 4, got ", req);
+  return (int)req;
+}
+
+// Launches gemm_skinny_v2_kernel<MT, EPI> (depth 2) or the ring kernel at
+// `depth`.
+template <int MT, int EPI, typename... Args>
+static void launch_skinny_v2(int depth, dim3 grid, Args... args) {
+  if (depth == 2)
+    gemm_skinny_v2_kernel<MT, EPI><<<grid, 256, 0, cur_stream()>>>(args...);
+  else
+    gemm_skinny_v2_ring_kernel<MT, EPI, 4><<<grid, 256, 0, cur_stream()>>>(args...);
+}
+
 struct W4Plan {
   bool gemv;
   int ksplit, kchunk;
@@ -244,6 +277,18 @@ static SplitK moe_w4_plan(long E, long N, long K, long S, long ksplit_req) {
 std::tuple<long, long, bool> gemm_skinny_plan(long N, long K, long ksplit_req) {
   const SkinnyPlan p = skinny_plan(N, K, ksplit_req);
   return {p.ksplit, p.kchunk, p.v2};
+}
+
+// The ring depth gemm_skinny (or, ksplit_req == 1, gemm_skinny_swiglu) takes
+// for an (N, K) weight, 0 where the shape runs on the v1 kernel; and the
+// depths the kernel is built at.
+std::tuple<long, std::vector<long>> gemm_skinny_wring_plan(long N, long K,
+                                                           long ksplit_req,
+                                                           long wring_req) {
+  const SkinnyPlan p = skinny_plan(N, K, ksplit_req);
+  const std::vector<long> built(std::begin(kWringDepths), std::end(kWringDepths));
+  if (!p.v2) return {0, built};
+  return {skinny_wring(wring_req), built};
 }
 
 std::tuple<bool, long, long> gemm_w4_plan(long M, long N, long K, long ksplit_req) {
@@ -941,15 +986,19 @@ static void rope_kv_write_launch(
   const float* sp = ops.ptr<F32>(sin_t, "sin_t");
   const int* posp = ops.ptr<I32>(pos, "pos", true, partp ? (long)B * T : -1);
   const int* spp = ops.ptr<I32>(start_pos, "start_pos", true, start_numel);
-  dim3 grid(B * T, Hq + 2 * Hkv);
-  if (partp)
-    rope_kv_write_kernel<true><<<grid, 64, 0, cur_stream()>>>(
+  if (partp) {
+    // one lane per pair of 16 B groups of the row: (Hq+2Hkv)*D/8 items
+    const int items = (Hq + 2 * Hkv) * (kv.D / 8);
+    dim3 grid(B * T, (items + 255) / 256);
+    rope_kv_write_part_kernel<<<grid, 256, 0, cur_stream()>>>(
         qkvp, partp, biasp, nslab, cp, sp, posp, kv.k, kv.v, kv.pt, spp, B, Hq,
         Hkv, T, kv.D, kv.P, kv.maxp, (int)cos_t.size(0), ctxp);
-  else
-    rope_kv_write_kernel<false><<<grid, 64, 0, cur_stream()>>>(
-        qkvp, nullptr, nullptr, 0, cp, sp, posp, kv.k, kv.v, kv.pt, spp, B, Hq,
-        Hkv, T, kv.D, kv.P, kv.maxp, (int)cos_t.size(0));
+  } else {
+    dim3 grid(B * T, Hq + 2 * Hkv);
+    rope_kv_write_kernel<<<grid, 64, 0, cur_stream()>>>(
+        qkvp, cp, sp, posp, kv.k, kv.v, kv.pt, spp, B, Hq, Hkv, T, kv.D, kv.P,
+        kv.maxp, (int)cos_t.size(0));
+  }
 }
 
 void rope_kv_write_(torch::Tensor qkv, long Hq_, long Hkv_, torch::Tensor cos_t,
@@ -1164,7 +1213,7 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
                           c10::optional<torch::Tensor> ss_in,
                           c10::optional<torch::Tensor> ss_out,
                           long norm_mode_req, bool defer_combine,
-                          c10::optional<torch::Tensor> cnt) {
+                          c10::optional<torch::Tensor> cnt, long wring_req) {
   // defer_combine: under split-K skip the combine and return the f32 slabs
   // (ksplit, M, N) for a consumer that folds them itself (rope_kv_write_part);
   // bias is then the consumer's to add. With ksplit == 1 there is nothing to
@@ -1172,6 +1221,8 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
   // cnt: (>= N/64,) int32 zeros — under split-K on the v2 kernel the combine
   // runs inside the GEMM launch (last-arriver reduction); the kernel leaves
   // the counters zero again.
+  // wring: W ring depth of the v2 kernel for this call (skinny_wring); 0
+  // leaves it to BBAMD_GEMM_WRING and the rule.
   Operands ops(A, "A");
   const auto* ap = ops.ptr<Bf16>(A, "A");
   const auto* wp = ops.ptr<Bf16>(W, "W");
@@ -1205,25 +1256,32 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
   const SkinnyPlan plan = skinny_plan(N, K, ksplit_req);
   const int ksplit = plan.ksplit, kchunk = plan.kchunk;
   const Slabs part = alloc_slabs(ops, A, ksplit, M, N);
+  // mode 1 scales A in registers as it stages; the ring has none to spare
+  const int wring =
+      !plan.v2 ? 0
+      : norm_mode == 1
+          ? 2
+          : skinny_wring(wring_req);
   if (cnt.has_value() && ksplit > 1 && plan.v2) {
     TORCH_CHECK(!defer_combine, "cnt and defer_combine exclude each other");
     TORCH_CHECK(cnt->numel() >= N / 64, "cnt must be int32 of >= N/64 entries");
     // combine inside the launch: 1-D grid, tile = id / ksplit after the remap
     dispatch_mtile(M, [&](auto mt) {
-      gemm_skinny_v2_kernel<decltype(mt)::value, 2>
-          <<<dim3((N / 64) * ksplit), 256, 0, cur_stream()>>>(
-              ap, wp, rp, bp, cp, part.p, M, N, K, kchunk, ksplit, nwp,
-              (float)eps, norm_mode, ssinp, nstripes, ssoutp, cntp);
+      launch_skinny_v2<decltype(mt)::value, 2>(
+          wring, dim3((N / 64) * ksplit), ap, wp, rp, bp, cp, part.p, M, N, K,
+          kchunk, ksplit, nwp, (float)eps, norm_mode, ssinp, nstripes, ssoutp,
+          cntp);
     });
     return C;
   }
   dim3 grid(N / 64, ksplit);
   dispatch_mtile(M, [&](auto mt) {
     if (plan.v2)
-      gemm_skinny_v2_kernel<decltype(mt)::value><<<grid, 256, 0, cur_stream()>>>(
-          ap, wp, ksplit == 1 ? rp : nullptr, ksplit == 1 ? bp : nullptr, cp,
-          part.p, M, N, K, kchunk, ksplit, nwp, (float)eps, norm_mode, ssinp,
-          nstripes, ksplit == 1 ? ssoutp : nullptr);
+      launch_skinny_v2<decltype(mt)::value, 0>(
+          wring, grid, ap, wp, ksplit == 1 ? rp : nullptr,
+          ksplit == 1 ? bp : nullptr, cp, part.p, M, N, K, kchunk, ksplit, nwp,
+          (float)eps, norm_mode, ssinp, nstripes,
+          ksplit == 1 ? ssoutp : nullptr, (int*)nullptr);
     else {
       TORCH_CHECK(!norm_mode && (!ssoutp || ksplit > 1),
                   "fused norm / ss_out need the v2 (K%256) kernel");
@@ -1262,7 +1320,7 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
 // swiglu(gemm_skinny(A, W, ...)).
 torch::Tensor gemm_skinny_swiglu(torch::Tensor A, torch::Tensor W, double eps,
                                  c10::optional<torch::Tensor> ss_in,
-                                 long norm_mode_req) {
+                                 long norm_mode_req, long wring_req) {
   Operands ops(A, "A");
   const auto* ap = ops.ptr<Bf16>(A, "A");
   const auto* wp = ops.ptr<Bf16>(W, "W");
@@ -1284,11 +1342,13 @@ torch::Tensor gemm_skinny_swiglu(torch::Tensor A, torch::Tensor W, double eps,
   sizes.back() = I;
   auto C = torch::empty(sizes, A.options());
   auto* cp = ops.ptr<Bf16>(C, "C");
+  const int wring = skinny_wring(wring_req);
   dispatch_mtile(M, [&](auto mt) {
-    gemm_skinny_v2_kernel<decltype(mt)::value, 1>
-        <<<dim3(I / 32), 256, 0, cur_stream()>>>(
-            ap, wp, nullptr, nullptr, cp, nullptr, M, N, K, K, 1, nullptr,
-            (float)eps, norm_mode, ssinp, nstripes, nullptr, nullptr);
+    launch_skinny_v2<decltype(mt)::value, 1>(
+        wring, dim3(I / 32), ap, wp, (const unsigned short*)nullptr,
+        (const unsigned short*)nullptr, cp, (float*)nullptr, M, N, K, K, 1,
+        (const unsigned short*)nullptr, (float)eps, norm_mode, ssinp, nstripes,
+        (float*)nullptr, (int*)nullptr);
   });
   return C;
 }
@@ -1390,11 +1450,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ksplit") = 0, py::arg("norm_w") = c10::nullopt,
         py::arg("eps") = 0.0, py::arg("ss_in") = c10::nullopt,
         py::arg("ss_out") = c10::nullopt, py::arg("norm_mode") = 0,
-        py::arg("defer_combine") = false, py::arg("cnt") = c10::nullopt);
+        py::arg("defer_combine") = false, py::arg("cnt") = c10::nullopt,
+        py::arg("wring") = 0);
   m.def("gemm_skinny_swiglu", &gemm_skinny_swiglu, py::arg("A"), py::arg("W"),
         py::arg("eps") = 0.0, py::arg("ss_in") = c10::nullopt,
-        py::arg("norm_mode") = 0);
+        py::arg("norm_mode") = 0, py::arg("wring") = 0);
   m.def("gemm_skinny_plan", &gemm_skinny_plan);
+  m.def("gemm_skinny_wring_plan", &gemm_skinny_wring_plan, py::arg("N"),
+        py::arg("K"), py::arg("ksplit") = 0, py::arg("wring") = 0);
   m.def("rope_kv_write_part", &rope_kv_write_part);
   m.def("moe_gemm", &moe_gemm);
   m.def("gemm_w4", &gemm_w4);

@@ -175,8 +175,38 @@ DEVINL void gemm_skinny_combine_lane(
 //     acquires, folds all slabs with gemm_skinny_combine_lane (the separate
 //     combine kernel's epilogue, same bits) and resets the counter. Nobody
 //     waits on anybody: no polling, nothing to hang.
-template <int MT, int EPI = 0>
-__global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(
+//
+// DEPTH is the number of W register sets (4 KB per wave each) a wave keeps
+// requested. 2 is the form described above: one set outstanding at each wait.
+// DEPTH > 2 is a ring: the A stage grows to one ring period (DEPTH * 128 k),
+// the prologue requests A first and then the whole ring, and each set is
+// re-requested for the next period as soon as its MFMAs have consumed it, so
+// DEPTH - 1 sets stay in flight at every wait. vmcnt retires in order, which
+// fixes the order of issue: the next period's A is requested BEFORE this
+// period's re-requests, so the wait for it at the period's end leaves all
+// DEPTH sets flying. Register sets are indexed statically: the loop body is
+// one unrolled period with every request unconditional, and the last one or
+// two periods are peeled per remaining set count (a conditional request would
+// make the compiler's wait counts assume the shortest path and drain the
+// ring). Per accumulator the MFMA order is k ascending in steps of 32 at
+// every DEPTH, so all depths produce the same bits. Norm mode 1 exists at
+// DEPTH 2 only (the host never launches the ring with it).
+template <int I>
+struct WringIdx {
+  static constexpr int value = I;
+};
+
+// f(WringIdx<n>) for the even n in [N, 2 * DEPTH - 2] equal to nrem
+template <int DEPTH, int N, typename F>
+DEVINL void wring_tail_dispatch(int nrem, F& f) {
+  if constexpr (N <= 2 * DEPTH - 2) {
+    if (nrem == N) f(WringIdx<N>{});
+    else wring_tail_dispatch<DEPTH, N + 2>(nrem, f);
+  }
+}
+
+template <int MT, int EPI, int DEPTH>
+DEVINL void gemm_skinny_v2_body(
     const unsigned short* __restrict__ A,   // (M, K) bf16
     const unsigned short* __restrict__ W,   // (N, K) bf16
     const unsigned short* __restrict__ R,   // (M, N) bf16 residual or null
@@ -192,10 +222,13 @@ __global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(
     const float* __restrict__ ssin,   // (nstripes, 32) producer row sum-sq
     int nstripes,
     float* __restrict__ ssout,        // (N/64, 32) this GEMM's row sum-sq
-    int* cnt = nullptr) {             // EPI 2: (N/64,) tickets, zero on entry
+    int* cnt) {             // EPI 2: (N/64,) tickets, zero on entry
+  static_assert(DEPTH == 2 || DEPTH % 4 == 0, "ring: whole waves per A row");
   constexpr int U = 4;                     // k-slices per pipeline set (128 k)
-  constexpr int KSTEP = 256;               // A elements staged per stage
+  constexpr int KSTEP = DEPTH * 128;       // A elements staged per stage
   constexpr int RSTRIDE = KSTEP + 8;       // padded LDS row stride (elements)
+  constexpr int RPIECE = KSTEP / 8;        // 16 B pieces per staged A row
+  constexpr int NPIECE = (32 * KSTEP) / (256 * 8);  // pieces per thread
   __shared__ __attribute__((aligned(16))) unsigned short atile[32 * RSTRIDE];
   // Fused rmsnorm of A (nw != null): removes the separate rms_norm launch +
   // its read/write from the decode step (launch-count reduction — the PMC
@@ -241,35 +274,52 @@ __global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(
 
   // ---- A staging: the whole workgroup copies A[0:M][ks:ks+256] with
   // full-line loads; rows beyond M-1 are clamped (their C rows are dropped).
-  // Thread piece j: row = (tid + j*256)/32 clamped, 8 elements at
-  // ((tid + j*256)%32)*8 within the stage.
-  short8 aregs[(32 * KSTEP) / (256 * 8)];  // 4 pieces per thread
-  short8 nregs[(32 * KSTEP) / (256 * 8)];  // matching norm-weight pieces
-  auto load_a = [&](int ks) {
+  // Thread piece j: row = (tid + j*256)/RPIECE clamped, 8 elements at
+  // ((tid + j*256)%RPIECE)*8 within the stage. `lim` (a multiple of 128) is
+  // how much of the stage lies inside the split: pieces past it re-read the
+  // last valid one and are never consumed.
+  short8 aregs[NPIECE];                    // 4 pieces per thread at DEPTH 2
+  // matching norm-weight pieces (mode 1). The ring spends these registers on
+  // W: mode 1 is not built for it and the host keeps such calls at DEPTH 2.
+  short8 nregs[DEPTH == 2 ? NPIECE : 1];
+  // In the ring a wave's piece j is 64 consecutive pieces of ONE row (RPIECE
+  // is a multiple of 64): the row part of the address is wave-uniform and
+  // stays in scalar registers, the lanes share one 32-bit byte offset.
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+  auto load_a = [&](int ks, int lim = 1 << 30) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int flat = threadIdx.x + j * 256;
-      const int row = min(flat / 32, M - 1);
-      const int off = (flat % 32) * 8;
-      aregs[j] = *reinterpret_cast<const short8*>(A + (long)row * K + ks + off);
-      if (norm_mode == 1)
-        nregs[j] = *reinterpret_cast<const short8*>(nw + ks + off);
+    for (int j = 0; j < NPIECE; ++j) {
+      if constexpr (DEPTH == 2) {
+        const int flat = threadIdx.x + j * 256;
+        const int row = min(flat / RPIECE, M - 1);
+        const int off = (flat % RPIECE) * 8;
+        aregs[j] = *reinterpret_cast<const short8*>(A + (long)row * K + ks + off);
+        if (norm_mode == 1)
+          nregs[j] = *reinterpret_cast<const short8*>(nw + ks + off);
+      } else {
+        const int fw = wave_s + j * 4;       // (tid + j*256) / 64
+        const int row = min(fw / (RPIECE / 64), M - 1);
+        const unsigned off =
+            min((fw % (RPIECE / 64)) * 64 + lane, lim / 8 - 1) * 16u;  // bytes
+        aregs[j] = *reinterpret_cast<const short8*>(
+            reinterpret_cast<const char*>(A + (long)row * K + ks) + off);
+      }
     }
   };
   auto store_a = [&]() {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < NPIECE; ++j) {
       const int flat = threadIdx.x + j * 256;
       short8 v = aregs[j];
-      if (norm_mode == 1) {
-        const float ir = invr[flat / 32 >= M ? M - 1 : flat / 32];
+      if (DEPTH == 2 && norm_mode == 1) {
+        const float ir = invr[flat / RPIECE >= M ? M - 1 : flat / RPIECE];
 #pragma unroll
         for (int e = 0; e < 8; ++e)
           v[e] = (short)f2bf(bf2f((unsigned short)v[e]) * ir *
                              bf2f((unsigned short)nregs[j][e]));
       }
-      *reinterpret_cast<short8*>(atile + (flat / 32) * RSTRIDE + (flat % 32) * 8) =
-          v;
+      *reinterpret_cast<short8*>(atile + (flat / RPIECE) * RSTRIDE +
+                                 (flat % RPIECE) * 8) = v;
     }
   };
 
@@ -286,9 +336,9 @@ __global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(
       bB1[u] = as_bf16x8(
           *reinterpret_cast<const short8*>(wrow + k + u * 32 + hi * 8));
   };
-  // A fragment for m-tile t, k-slice u of the staged 256: ds_read_b128 at
-  // row (t*16 + li), element (u*32 + hi*8) — row stride 528 B => lanes hit
-  // distinct banks.
+  // A fragment for m-tile t, k-slice u of 128-k set `half` of the stage:
+  // ds_read_b128 at row (t*16 + li), element (half*128 + u*32 + hi*8) — the
+  // row stride is 16 B past a multiple of 512 B => lanes hit distinct banks.
   auto mfma_set = [&](bf16x8* bB, int half) {
 #pragma unroll
     for (int u = 0; u < U; ++u)
@@ -352,35 +402,100 @@ __global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(
     }
   };
 
-  if (norm_mode == 1) {
-    // mode 1 scales A as it stages: invr must exist BEFORE the pipeline.
-    // Issue the first W-register set first so the stream is in flight.
-    issue0(k0);
-    reduce_invr();
-    load_a(k0);
-    store_a();
-    __syncthreads();
-  } else {
-    // Pipeline: stage s's A sits in LDS while its two B register sets
-    // stream; stage s+1's A loads issue right after the barrier frees them.
-    // mode 2 defers its invr reduce to just before the epilogue — the
-    // weight stream starts with zero added latency.
-    load_a(k0);
-    issue0(k0);
-    store_a();
-    __syncthreads();
-  }
-  for (int k = k0; k < k1; k += KSTEP) {
-    if (k + KSTEP < k1) load_a(k + KSTEP);
-    issue1(k + 128);
-    mfma_set(bB0, 0);
-    if (k + KSTEP < k1) issue0(k + KSTEP);
-    mfma_set(bB1, 1);
-    if (k + KSTEP < k1) {
-      __syncthreads();  // everyone done reading stage s
+  if constexpr (DEPTH == 2) {
+    if (norm_mode == 1) {
+      // mode 1 scales A as it stages: invr must exist BEFORE the pipeline.
+      // Issue the first W-register set first so the stream is in flight.
+      issue0(k0);
+      reduce_invr();
+      load_a(k0);
+      store_a();
+      __syncthreads();
+    } else {
+      // Pipeline: stage s's A sits in LDS while its two B register sets
+      // stream; stage s+1's A loads issue right after the barrier frees them.
+      // mode 2 defers its invr reduce to just before the epilogue — the
+      // weight stream starts with zero added latency.
+      load_a(k0);
+      issue0(k0);
       store_a();
       __syncthreads();
     }
+    for (int k = k0; k < k1; k += KSTEP) {
+      if (k + KSTEP < k1) load_a(k + KSTEP);
+      issue1(k + 128);
+      mfma_set(bB0, 0);
+      if (k + KSTEP < k1) issue0(k + KSTEP);
+      mfma_set(bB1, 1);
+      if (k + KSTEP < k1) {
+        __syncthreads();  // everyone done reading stage s
+        store_a();
+        __syncthreads();
+      }
+    }
+  } else {
+    bf16x8 ring[DEPTH][U];
+    auto issue = [&](int j, int k) {
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        ring[j][u] = as_bf16x8(
+            *reinterpret_cast<const short8*>(wrow + k + u * 32 + hi * 8));
+    };
+    // A stream shorter than the ring re-reads its last set into the spare
+    // registers: every request stays unconditional.
+    auto issue_ring = [&]() {
+#pragma unroll
+      for (int j = 0; j < DEPTH; ++j) issue(j, min(k0 + j * 128, k1 - 128));
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    // A first: the wait for it leaves the whole ring in flight
+    load_a(k0, min(KSTEP, k1 - k0));
+    __builtin_amdgcn_sched_barrier(0);
+    issue_ring();
+    store_a();
+    __syncthreads();
+    int k = k0;
+    // whole periods with a whole period behind them
+    for (; k + 2 * KSTEP <= k1; k += KSTEP) {
+      load_a(k + KSTEP);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < DEPTH; ++j) {
+        mfma_set(ring[j], j);
+        issue(j, k + KSTEP + j * 128);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      __syncthreads();  // everyone done reading this period's A
+      store_a();
+      __syncthreads();
+    }
+    // NREM sets are left: min(NREM, DEPTH) in the ring, the rest a partial
+    // last period
+    auto tail = [&](auto nrem_c) {
+      constexpr int NREM = decltype(nrem_c)::value;
+      constexpr int CUR = NREM < DEPTH ? NREM : DEPTH;
+      constexpr int NEXT = NREM - CUR;
+      if constexpr (NEXT > 0) {
+        load_a(k + KSTEP, NEXT * 128);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int j = 0; j < CUR; ++j) {
+        mfma_set(ring[j], j);
+        if (j < NEXT) {
+          issue(j, k + KSTEP + j * 128);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      if constexpr (NEXT > 0) {
+        __syncthreads();
+        store_a();
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < NEXT; ++j) mfma_set(ring[j], j);
+      }
+    };
+    wring_tail_dispatch<DEPTH, 2>((k1 - k) / 128, tail);
   }
 
   if (norm_mode == 2) reduce_invr();
@@ -525,6 +640,32 @@ __global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(
         dst[(long)m * N + n0 + li] = v;
       }
   }
+}
+
+// The kernels proper. DEPTH 2 keeps the name and the launch bounds it has
+// always had; the ring asks for 3 workgroups per CU (the qkv grid places 3),
+// which caps it at 168 registers.
+#define SKINNY_V2_PARAMS                                                      \
+  const unsigned short *__restrict__ A, const unsigned short *__restrict__ W, \
+      const unsigned short *__restrict__ R,                                   \
+      const unsigned short *__restrict__ bias, unsigned short *__restrict__ C, \
+      float *__restrict__ Cpart, int M, int N, int K, int kchunk, int ksplit, \
+      const unsigned short *__restrict__ nw, float eps, int norm_mode,        \
+      const float *__restrict__ ssin, int nstripes, float *__restrict__ ssout, \
+      int *cnt
+#define SKINNY_V2_ARGS                                                       \
+  A, W, R, bias, C, Cpart, M, N, K, kchunk, ksplit, nw, eps, norm_mode, ssin, \
+      nstripes, ssout, cnt
+
+template <int MT, int EPI = 0>
+__global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(SKINNY_V2_PARAMS) {
+  gemm_skinny_v2_body<MT, EPI, 2>(SKINNY_V2_ARGS);
+}
+
+template <int MT, int EPI, int DEPTH>
+__global__ __launch_bounds__(256, 3) void gemm_skinny_v2_ring_kernel(
+    SKINNY_V2_PARAMS) {
+  gemm_skinny_v2_body<MT, EPI, DEPTH>(SKINNY_V2_ARGS);
 }
 
 // Split-K combine that also emits per-stripe row sum-of-squares (ssout
