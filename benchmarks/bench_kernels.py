@@ -211,6 +211,43 @@ def bench_norms():
         print(f"rms_norm_res ({N},{H}): {t*1e6:7.1f} us  {5*N*H*2/t/1e12:5.2f} TB/s")
 
 
+def bench_layer_norm():
+    """layer_norm beside rms_norm at decode-batch shapes of the LayerNorm
+    families (Falcon-7B H = 4544, BLOOM-176B H = 14336). A window is 2000
+    back-to-back calls between two device events; three rounds of 10
+    windows, the median window per round, and the spread over the rounds
+    next to it (compare two builds only beyond that spread)."""
+    def per_call(fn, calls=2000, windows=10):
+        for _ in range(200):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(windows):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            b.synchronize()
+            ts.append(a.elapsed_time(b) * 1e-3 / calls)
+        ts.sort()
+        return ts[len(ts) // 2]
+
+    for N, H in [(32, 4544), (32, 14336)]:
+        gen = torch.Generator(device=DEV).manual_seed(H)
+        x = torch.randn(N, H, generator=gen, device=DEV).to(torch.bfloat16)
+        w = torch.randn(H, generator=gen, device=DEV).to(torch.bfloat16)
+        b = torch.randn(H, generator=gen, device=DEV).to(torch.bfloat16)
+        tl, tr = [], []
+        for _ in range(3):
+            tl.append(per_call(lambda: ops.layer_norm(x, w, b)))
+            tr.append(per_call(lambda: ops.rms_norm(x, w)))
+        tl.sort(), tr.sort()
+        print(f"layer_norm ({N},{H}): {tl[1]*1e6:7.2f} us [{tl[0]*1e6:.2f}..{tl[2]*1e6:.2f}]"
+              f"   rms_norm: {tr[1]*1e6:7.2f} us [{tr[0]*1e6:.2f}..{tr[2]*1e6:.2f}]"
+              f"   (call time, launch included)", flush=True)
+
+
 def bench_swiglu():
     for N, I in [(32, 14336), (16384, 14336)]:
         gu = torch.randn(N, 2 * I, dtype=torch.bfloat16, device=DEV)
@@ -406,6 +443,7 @@ ALL = {
     "train_attn": bench_train_attn,
     "kv_stream": bench_kv_stream,
     "norms": bench_norms,
+    "layer_norm": bench_layer_norm,
     "swiglu": bench_swiglu,
     "gemm": bench_gemm,
     "gemm_norm": bench_gemm_norm,

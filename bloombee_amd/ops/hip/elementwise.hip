@@ -85,7 +85,7 @@ __global__ __launch_bounds__(BLOCK) void layernorm_kernel(
   const unsigned short* rr = res ? res + row * (long)H : nullptr;
 
   float v[ITERS][8];
-  float s1 = 0.f, s2 = 0.f;
+  float s1 = 0.f;
 #pragma unroll
   for (int it = 0; it < ITERS; ++it) {
     int d = (it * BLOCK + threadIdx.x) * 8;
@@ -99,22 +99,42 @@ __global__ __launch_bounds__(BLOCK) void layernorm_kernel(
         if (out_h) store_bf16x8(out_h + row * (long)H + d, v[it]);
       }
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { s1 += v[it][j]; s2 += v[it][j] * v[it][j]; }
+      for (int j = 0; j < 8; ++j) s1 += v[it][j];
     }
   }
-  s1 = wave_reduce_sum(s1);
-  s2 = wave_reduce_sum(s2);
+  // The variance is sum((v - mu)^2) over the row held in registers, after a
+  // block reduction for mu of its own. The one-pass form t2/H - mu*mu cancels
+  // catastrophically in f32 when |mu| >> sigma: it went negative (NaN row)
+  // on near-constant rows at H = 14336 and lost 0.3 % of the scale at
+  // |mu|/sigma = 250.
   __shared__ float ws1[BLOCK / WAVE], ws2[BLOCK / WAVE];
-  if ((threadIdx.x & (WAVE - 1)) == 0) {
-    ws1[threadIdx.x / WAVE] = s1;
-    ws2[threadIdx.x / WAVE] = s2;
-  }
+  s1 = wave_reduce_sum(s1);
+  if ((threadIdx.x & (WAVE - 1)) == 0) ws1[threadIdx.x / WAVE] = s1;
   __syncthreads();
-  float t1 = 0.f, t2 = 0.f;
+  float t1 = 0.f;
 #pragma unroll
-  for (int i = 0; i < BLOCK / WAVE; ++i) { t1 += ws1[i]; t2 += ws2[i]; }
+  for (int i = 0; i < BLOCK / WAVE; ++i) t1 += ws1[i];
   const float mu = t1 / (float)H;
-  const float inv = rsqrtf(t2 / (float)H - mu * mu + eps);
+
+  float s2 = 0.f;
+#pragma unroll
+  for (int it = 0; it < ITERS; ++it) {
+    int d = (it * BLOCK + threadIdx.x) * 8;
+    if (d < H) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float c = v[it][j] - mu;
+        s2 += c * c;
+      }
+    }
+  }
+  s2 = wave_reduce_sum(s2);
+  if ((threadIdx.x & (WAVE - 1)) == 0) ws2[threadIdx.x / WAVE] = s2;
+  __syncthreads();
+  float t2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < BLOCK / WAVE; ++i) t2 += ws2[i];
+  const float inv = rsqrtf(t2 / (float)H + eps);
 
 #pragma unroll
   for (int it = 0; it < ITERS; ++it) {

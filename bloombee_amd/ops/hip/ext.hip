@@ -125,6 +125,16 @@ static PagedKV paged_kv(const Operands& ops, const torch::Tensor& k_pages,
   return kv;
 }
 
+// What kv_write / kv_gather need beyond paged_kv(): they move 16 B (8 bf16)
+// at a time along D, and index V d-major.
+static void check_kv_copy_layout(const PagedKV& kv, const torch::Tensor& k_pages,
+                                 const torch::Tensor& v_pages) {
+  TORCH_CHECK(kv.D >= 8 && kv.D % 8 == 0, "head_dim must be a multiple of 8, got ", kv.D);
+  TORCH_CHECK(v_pages.size(0) == k_pages.size(0) && v_pages.size(1) == kv.Hkv &&
+                  v_pages.size(2) == kv.D && v_pages.size(3) == kv.P,
+              "v_pages must be d-major (np, Hkv, D, P)");
+}
+
 // ---------------------------------------------------------------------------
 // template dispatch
 // ---------------------------------------------------------------------------
@@ -329,10 +339,14 @@ static dim3 moe_grid(int N, long E, long mchunks, int ksplit) {
 // norms
 // ---------------------------------------------------------------------------
 
+// The norm kernels' launch rule, for all three ops: a lane owns 16 B (8 bf16)
+// of the row per iteration, so an H that is no multiple of 8 would read and
+// write past the row; at most 8 iterations of 256 lanes. Raises before f runs.
 template <typename F>
 static void dispatch_iters(int H, F f) {
   constexpr int BLOCK = 256;
   const int per_iter = BLOCK * 8;
+  TORCH_CHECK(H >= 8 && H % 8 == 0, "norm kernels need H % 8 == 0, got ", H);
   if (H <= per_iter) f(std::integral_constant<int, 1>{});
   else if (H <= 2 * per_iter) f(std::integral_constant<int, 2>{});
   else if (H <= 4 * per_iter) f(std::integral_constant<int, 4>{});
@@ -344,12 +358,12 @@ torch::Tensor rms_norm(torch::Tensor x, torch::Tensor w, double eps) {
   Operands ops(x, "x");
   const auto* xp = ops.ptr<Bf16>(x, "x");
   const int H = x.size(-1);
-  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
-  const long N = x.numel() / H;
+  const long N = H > 0 ? x.numel() / H : 0;
   const auto* wp = ops.ptr<Bf16>(w, "w", true, H);
   auto y = torch::empty_like(x);
   auto* yp = ops.ptr<Bf16>(y, "y");
   dispatch_iters(H, [&](auto iters) {
+    if (N == 0) return;  // no rows: nothing to launch
     rmsnorm_kernel<256, decltype(iters)::value><<<N, 256, 0, cur_stream()>>>(
         xp, nullptr, wp, nullptr, yp, H, (float)eps);
   });
@@ -362,13 +376,14 @@ std::vector<torch::Tensor> rms_norm_residual(torch::Tensor x, torch::Tensor res,
   const auto* xp = ops.ptr<Bf16>(x, "x");
   const auto* rp = ops.ptr<Bf16>(res, "res", true, x.numel());
   const int H = x.size(-1);
-  const long N = x.numel() / H;
+  const long N = H > 0 ? x.numel() / H : 0;
   const auto* wp = ops.ptr<Bf16>(w, "w", true, H);
   auto h = torch::empty_like(x);
   auto y = torch::empty_like(x);
   auto* hp = ops.ptr<Bf16>(h, "h");
   auto* yp = ops.ptr<Bf16>(y, "y");
   dispatch_iters(H, [&](auto iters) {
+    if (N == 0) return;
     rmsnorm_kernel<256, decltype(iters)::value><<<N, 256, 0, cur_stream()>>>(
         xp, rp, wp, hp, yp, H, (float)eps);
   });
@@ -380,12 +395,13 @@ torch::Tensor layer_norm(torch::Tensor x, torch::Tensor w,
   Operands ops(x, "x");
   const auto* xp = ops.ptr<Bf16>(x, "x");
   const int H = x.size(-1);
-  const long N = x.numel() / H;
+  const long N = H > 0 ? x.numel() / H : 0;
   const auto* wp = ops.ptr<Bf16>(w, "w", true, H);
   const auto* bp = ops.ptr<Bf16>(bias, "bias", true, H);
   auto y = torch::empty_like(x);
   auto* yp = ops.ptr<Bf16>(y, "y");
   dispatch_iters(H, [&](auto iters) {
+    if (N == 0) return;
     layernorm_kernel<256, decltype(iters)::value><<<N, 256, 0, cur_stream()>>>(
         xp, nullptr, wp, bp, nullptr, yp, H, (float)eps);
   });
@@ -404,9 +420,18 @@ void rope_apply_(torch::Tensor q, torch::Tensor k, torch::Tensor cos_t,
   const auto* cp = ops.ptr<F32>(cos_t, "cos_t");
   const auto* sp = ops.ptr<F32>(sin_t, "sin_t");
   const auto* pp = ops.ptr<I32>(pos, "pos");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "rope_apply_: q and k must be (B, H, T, D)");
   const int B = q.size(0), Hq = q.size(1), T = q.size(2), D = q.size(3);
   const int Hkv = k.size(1);
-  TORCH_CHECK(cos_t.size(1) == D / 2);
+  TORCH_CHECK(k.size(0) == B && k.size(2) == T && k.size(3) == D,
+              "rope_apply_: k must agree with q in B, T and D");
+  TORCH_CHECK(D % 2 == 0, "rope_apply_: head_dim must be even, got ", D);
+  TORCH_CHECK(pos.numel() == (long)B * T, "rope_apply_: pos must have B*T = ",
+              (long)B * T, " elements, got ", pos.numel());
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(0) >= 1 && cos_t.size(1) == D / 2 &&
+                  sin_t.sizes() == cos_t.sizes(),
+              "rope_apply_: cos/sin must be (max_pos, D/2)");
+  if ((long)B * T * (Hq + Hkv) == 0) return;
   dim3 grid(B * T, Hq + Hkv);
   rope_kernel<<<grid, 64, 0, cur_stream()>>>(qp, kp, cp, sp, pp, B, Hq, Hkv, T, D,
                                              (int)cos_t.size(0));
@@ -416,12 +441,14 @@ torch::Tensor swiglu(torch::Tensor gu) {
   Operands ops(gu, "gu");
   const auto* gp = ops.ptr<Bf16>(gu, "gu");
   const long I = gu.size(-1) / 2;
+  TORCH_CHECK(I >= 8 && gu.size(-1) == 2 * I && I % 8 == 0,
+              "swiglu needs a (..., 2I) input with I % 8 == 0");
   const long N = gu.numel() / (2 * I);
-  TORCH_CHECK(I % 8 == 0);
   auto sizes = gu.sizes().vec();
   sizes.back() = I;
   auto out = torch::empty(sizes, gu.options());
   const long nvec = N * (I / 8);
+  if (nvec == 0) return out;
   const int grid = (int)std::min<long>((nvec + 255) / 256, 2048);
   swiglu_kernel<<<grid, 256, 0, cur_stream()>>>(gp, ops.ptr<Bf16>(out, "out"), N, I);
   return out;
@@ -463,12 +490,15 @@ void kv_write(torch::Tensor k_new, torch::Tensor v_new, torch::Tensor k_pages,
   const auto* knp = ops.ptr<Bf16>(k_new, "k_new");
   const auto* vnp = ops.ptr<Bf16>(v_new, "v_new", true, k_new.numel());
   const PagedKV kv = paged_kv(ops, k_pages, v_pages, page_table);
+  check_kv_copy_layout(kv, k_pages, v_pages);
   const auto* spp = ops.ptr<I32>(start_pos, "start_pos");
+  TORCH_CHECK(k_new.dim() == 4, "k_new must be (B, Hkv, T, D)");
   const int B = k_new.size(0), Hkv = k_new.size(1), T = k_new.size(2), D = k_new.size(3);
   const int P = kv.P;
   TORCH_CHECK(kv.Hkv == Hkv && kv.D == D);
-  TORCH_CHECK(v_pages.size(2) == D && v_pages.size(3) == P,
-              "v_pages must be d-major (np, Hkv, D, P)");
+  TORCH_CHECK(start_pos.numel() >= B && page_table.size(0) >= B,
+              "kv_write: start_pos and page_table need a row per batch row");
+  if ((long)B * T == 0) return;
   const int threads = std::min(256, Hkv * D / 8);
   kv_write_kernel<<<B * T, threads, 0, cur_stream()>>>(
       knp, vnp, kv.k, kv.v, kv.pt, spp, B, Hkv, T, D, P, kv.maxp);
@@ -479,10 +509,17 @@ std::vector<torch::Tensor> kv_gather(torch::Tensor k_pages, torch::Tensor v_page
                                      long ctx) {
   Operands ops(k_pages, "k_pages");
   const PagedKV kv = paged_kv(ops, k_pages, v_pages, page_table);
+  check_kv_copy_layout(kv, k_pages, v_pages);
   const int Hkv = kv.Hkv, D = kv.D;
+  TORCH_CHECK(batch_index >= 0 && batch_index < page_table.size(0),
+              "kv_gather: batch_index ", batch_index, " outside [0, ",
+              page_table.size(0), ")");
+  TORCH_CHECK(ctx >= 0 && ctx <= (long)kv.maxp * kv.P, "kv_gather: ctx ", ctx,
+              " outside [0, maxp * P = ", (long)kv.maxp * kv.P, "]");
   auto k = torch::empty({Hkv, ctx, D}, k_pages.options());
   auto v = torch::empty({Hkv, ctx, D}, v_pages.options());
   const long nvec = ctx * Hkv * (D / 8);
+  if (nvec == 0) return {k, v};
   const int grid = (int)std::min<long>((nvec + 255) / 256, 2048);
   kv_gather_kernel<<<grid, 256, 0, cur_stream()>>>(
       kv.k, kv.v, ops.ptr<Bf16>(k, "k"), ops.ptr<Bf16>(v, "v"), kv.pt,
@@ -1367,6 +1404,7 @@ std::vector<torch::Tensor> quant4_pack(torch::Tensor x) {
   auto scale = torch::empty({nrows, ncols / 64}, x.options().dtype(at::kHalf));
   auto zero = torch::empty_like(scale);
   const long ngroups = nrows * (ncols / 64);
+  if (ngroups == 0) return {packed, scale, zero};
   const int wpb = 4;  // waves per block
   quant4_pack_kernel<64><<<(ngroups + wpb - 1) / wpb, wpb * 64, 0, cur_stream()>>>(
       xp, ops.ptr<U8>(packed, "packed"), ops.ptr<F16>(scale, "scale"),
@@ -1385,6 +1423,7 @@ torch::Tensor quant4_unpack(torch::Tensor packed, torch::Tensor scale,
   auto* zp = ops.ptr<F16>(zero, "zero", true, nrows * (ncols / 64));
   auto out = torch::empty({nrows, ncols}, packed.options().dtype(at::kBFloat16));
   const long total = nrows * ncols;
+  if (total == 0) return out;
   const int grid = (int)std::min<long>((total + 255) / 256, 4096);
   quant4_unpack_kernel<64><<<grid, 256, 0, cur_stream()>>>(
       qp, scp, zp, ops.ptr<Bf16>(out, "out"), nrows, ncols);
