@@ -21,6 +21,7 @@ here; Qwen3 is this block plus the _post_qkv / _post_qkv_train hooks.
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import torch
@@ -32,6 +33,29 @@ from bloombee_amd.models.base import ModelConfig
 from bloombee_amd.models.block_common import (  # noqa: F401 (RopeTables: re-export)
     FamilyBlock, RopeTables, pack_q4, paged_attention_qkv, rms_train,
     rope_attn_train, rotary_positions, split_heads, swiglu_mlp_train)
+
+
+# Packed decode weights (ops.pack_skinny_w; profiles/r08_packed_w.md): a
+# second copy of a projection in the skinny GEMM kernel's read order, one
+# contiguous 1 KB per wave load. BBAMD_PACK_W (read at every call): "0" never
+# packs, "1" packs every projection of the fused-norm decode path, "auto"
+# packs the (N, K) shapes of _PACK_W_FASTER — those the flagship's kernel
+# trace measured faster packed; unmeasured shapes stay unpacked — and only
+# while free device memory after the copy stays >= 1/8 of the device's total
+# (a policy reserve for KV pages and activations, not a measurement).
+_PACK_W_DEFAULT = "auto"
+_PACK_W_FASTER: frozenset = frozenset((
+    (6144, 4096),       # qkv      13.8 -> 12.5 us
+    (4096, 4096),       # o         9.3 ->  8.3 us
+    (28672, 4096),      # gate_up  49.8 -> 41.6 us
+    (4096, 14336),      # down     25.0 -> 22.4 us
+))
+_PACK_W_RESERVE = 8     # keep total / 8 free
+
+
+def _pack_w_mode() -> str:
+    v = os.environ.get("BBAMD_PACK_W", _PACK_W_DEFAULT).strip().lower()
+    return v if v in ("0", "1") else "auto"
 
 
 class LlamaBlock(FamilyBlock):
@@ -62,6 +86,46 @@ class LlamaBlock(FamilyBlock):
         # int32 buffer, a slice of H/64 entries each for o-proj and down-proj;
         # zero between launches (the kernel resets what it counted)
         self._splitk_cnt = None
+        # packed decode weights: name -> (alias of the weight packed from,
+        # its _version then, packed copy or None where policy declined)
+        self._wpacked = {}
+
+    def _drop_packed(self) -> None:
+        self._wpacked.clear()
+
+    def _packed(self, name: str, swiglu: bool = False):
+        """Packed copy of projection `name` for ops.linear(w_packed=...) /
+        ops.linear_swiglu(w_packed=...), or None to run unpacked. Built once,
+        outside stream capture, and valid only for the very tensor it was
+        built from: the entry keeps that tensor's storage alive (so no other
+        tensor can take its address) and compares data_ptr and _version, so a
+        reassigned .data (fold / unfold, a move to another device) or an
+        in-place write (load_state_dict) rebuilds it on the next call."""
+        mode = _pack_w_mode()
+        if mode == "0":
+            self._drop_packed()
+            return None
+        w = getattr(self, name)
+        ent = self._wpacked.get(name)
+        if ent is not None:
+            src, ver, wp = ent
+            if src.data_ptr() == w.data_ptr() and ver == w._version:
+                return wp
+            del self._wpacked[name]
+        if w.is_cuda and torch.cuda.is_current_stream_capturing():
+            return None     # never allocate or pack inside a capture
+        wp = None
+        if mode == "1" or self._pack_auto_ok(w):
+            wp = ops.pack_skinny_w(w.detach(), swiglu)
+        self._wpacked[name] = (w.detach(), w._version, wp)
+        return wp
+
+    @staticmethod
+    def _pack_auto_ok(w: torch.Tensor) -> bool:
+        if tuple(w.shape) not in _PACK_W_FASTER or not w.is_cuda:
+            return False
+        free, total = torch.cuda.mem_get_info(w.device)
+        return free - w.numel() * w.element_size() >= total // _PACK_W_RESERVE
 
     def _fuse_norm_gate(self, hidden) -> bool:
         """All four decode GEMMs must hit the v2 kernel (K%256) with
@@ -94,6 +158,7 @@ class LlamaBlock(FamilyBlock):
         (profiles/r02 §13: the per-stage scale cost +4-8 us/GEMM)."""
         if getattr(self, "_norm_folded", False):
             return
+        self._drop_packed()
         self._norm_fold_orig = (self.input_norm_w.detach().clone(),
                                 self.post_norm_w.detach().clone())
         self.qkv_w.data = (self.qkv_w.float()
@@ -111,6 +176,7 @@ class LlamaBlock(FamilyBlock):
         adapters trained against the original parameterization."""
         if not getattr(self, "_norm_folded", False):
             return
+        self._drop_packed()
         inw, pnw = self._norm_fold_orig
         self.input_norm_w.data.copy_(inw)
         self.post_norm_w.data.copy_(pnw)
@@ -131,6 +197,7 @@ class LlamaBlock(FamilyBlock):
         flexgen_utils/compression.py:94-210). keep_full=False drops the
         bf16 weights (4x memory; the block becomes inference-only and
         prefill-shaped GEMMs dequantize on the fly)."""
+        self._drop_packed()
         pack_q4(self, ("qkv_w", "o_w", "gate_up_w", "down_w"), keep_full)
         return self
 
@@ -187,6 +254,9 @@ class LlamaBlock(FamilyBlock):
         self._ss_valid = False
         if fuse_norm and not getattr(self, "_norm_folded", False):
             self.fold_norm_weights()   # one-time reparameterization
+        if self._wpacked and (getattr(self, "_w4", None) is not None
+                              or getattr(self, "lora_delta", None) is not None):
+            self._drop_packed()        # W4 / LoRA closed the gate for good
         pb = getattr(self, "prev_block", None)
         # the qkv GEMM's split-K combine folds into rope_kv_write: the GEMM
         # hands over its f32 slabs and the combine launch disappears
@@ -198,10 +268,12 @@ class LlamaBlock(FamilyBlock):
             # norm weight is folded into qkv_w -> invr-only norm (mode 2)
             qkv = ops.linear(hidden, self.qkv_w,
                              norm=(None, cfg.rms_norm_eps),
-                             ss_in=pb._ss_hidden, defer_combine=defer)
+                             ss_in=pb._ss_hidden, defer_combine=defer,
+                             w_packed=self._packed("qkv_w"))
         elif defer:
             x = ops.rms_norm(hidden, self.input_norm_w, cfg.rms_norm_eps)
-            qkv = ops.linear(x, self.qkv_w, defer_combine=True)
+            qkv = ops.linear(x, self.qkv_w, defer_combine=True,
+                             w_packed=self._packed("qkv_w"))
         else:
             x = ops.rms_norm(hidden, self.input_norm_w, cfg.rms_norm_eps)
             qkv = self._lin(x, self.qkv_w, "qkv_w")        # (B, T, (Hq+2Hkv)D)
@@ -238,18 +310,24 @@ class LlamaBlock(FamilyBlock):
                             ss_out=self._ss_h2,
                             cnt=(self._splitk_cnt[:st]
                                  if ops.inlaunch_combine_ok(attn, self.o_w, "o")
-                                 else None))
+                                 else None),
+                            w_packed=self._packed("o_w"))
             # SwiGLU rides the gate_up GEMM's epilogue where available
             # (ops.linear_swiglu falls back to linear + swiglu, same bits)
             act = ops.linear_swiglu(h2, self.gate_up_w,
                                     norm=(None, cfg.rms_norm_eps),
-                                    ss_in=self._ss_h2)
+                                    ss_in=self._ss_h2,
+                                    w_packed=(self._packed("gate_up_w", True)
+                                              if ops.fuse_swiglu_ok(
+                                                  h2, self.gate_up_w)
+                                              else None))
             out = ops.linear(act, self.down_w, residual=h2,
                              ss_out=self._ss_hidden,
                              cnt=(self._splitk_cnt[st:]
                                   if ops.inlaunch_combine_ok(act, self.down_w,
                                                              "down")
-                                  else None))
+                                  else None),
+                             w_packed=self._packed("down_w"))
             self._ss_valid = True
             return out
         a = self._lin(attn, self.o_w, "o_w")

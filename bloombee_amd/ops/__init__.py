@@ -29,6 +29,7 @@ from bloombee_amd.ops.interface import (  # noqa: F401
     mfma_selftest,
     moe_gemm_grouped,
     moe_gemm_grouped_w4,
+    pack_skinny_w,
     quant4_pack,
     quant4_unpack,
     rms_norm,

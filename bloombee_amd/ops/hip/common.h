@@ -83,6 +83,20 @@ DEVINL float fast_expf(float x) { return __builtin_amdgcn_exp2f(x * LOG2E); }
 
 DEVINL long ldiv_up(long a, long b) { return (a + b - 1) / b; }
 
+// Pre-tiled ("packed") weight of the skinny GEMM's depth-2 kernel, for W (N, K)
+// bf16 with N % 16 == 0 and K % 32 == 0 (mirrored by pack_skinny_w in
+// ops/reference.py):
+//   Wp[g][kb][hi][li][e] = W[rowmap(g*16 + li)][kb*32 + hi*8 + e]
+// with g < N/16, kb < K/32, hi < 4, li < 16, e < 8. One (g, kb) block is 512
+// elements = 1 KB and lane-linear: lane hi*16 + li owns the 8 elements at
+// element lane*8. rowmap is the identity for the plain kernel and the SwiGLU
+// kernel's gate|up pairing for EPI 1 (g = tile*4 + wave: rows g*8 + li for
+// li < 8, N/2 + g*8 + li - 8 otherwise).
+static constexpr int SKINNY_PACK_BLOCK = 512;  // elements per (g, kb) block
+__host__ __device__ inline long skinny_packed_offset(int g, int kb, int K) {
+  return ((long)g * (K / 32) + kb) * SKINNY_PACK_BLOCK;
+}
+
 #define HIP_OK(expr)                                                         \
   do {                                                                       \
     hipError_t _e = (expr);                                                  \

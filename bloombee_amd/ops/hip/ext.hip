@@ -236,9 +236,18 @@ static int skinny_wring(long req) {
 }
 
 // Launches gemm_skinny_v2_kernel<MT, EPI> (depth 2) or the ring kernel at
-// `depth`.
+// `depth`. `packed`: the W among args is the pre-tiled copy, which only the
+// depth-2 kernel with the plain or the SwiGLU epilogue reads.
 template <int MT, int EPI, typename... Args>
-static void launch_skinny_v2(int depth, dim3 grid, Args... args) {
+static void launch_skinny_v2(int depth, bool packed, dim3 grid, Args... args) {
+  if constexpr (EPI != 2) {
+    if (packed) {
+      TORCH_CHECK(depth == 2, "packed W runs at ring depth 2 only");
+      gemm_skinny_v2_kernel<MT, EPI, true><<<grid, 256, 0, cur_stream()>>>(args...);
+      return;
+    }
+  }
+  TORCH_CHECK(!packed, "packed W: plain and SwiGLU epilogues only");
   if (depth == 2)
     gemm_skinny_v2_kernel<MT, EPI><<<grid, 256, 0, cur_stream()>>>(args...);
   else
@@ -1250,7 +1259,8 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
                           c10::optional<torch::Tensor> ss_in,
                           c10::optional<torch::Tensor> ss_out,
                           long norm_mode_req, bool defer_combine,
-                          c10::optional<torch::Tensor> cnt, long wring_req) {
+                          c10::optional<torch::Tensor> cnt, long wring_req,
+                          c10::optional<torch::Tensor> w_packed) {
   // defer_combine: under split-K skip the combine and return the f32 slabs
   // (ksplit, M, N) for a consumer that folds them itself (rope_kv_write_part);
   // bias is then the consumer's to add. With ksplit == 1 there is nothing to
@@ -1260,6 +1270,9 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
   // the counters zero again.
   // wring: W ring depth of the v2 kernel for this call (skinny_wring); 0
   // leaves it to BBAMD_GEMM_WRING and the rule.
+  // w_packed: W in the pre-tiled layout of common.h (identity row map),
+  // streamed instead of W where the call runs the depth-2 v2 kernel with the
+  // plain epilogue; every other path reads W.
   Operands ops(A, "A");
   const auto* ap = ops.ptr<Bf16>(A, "A");
   const auto* wp = ops.ptr<Bf16>(W, "W");
@@ -1299,23 +1312,26 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
       : norm_mode == 1
           ? 2
           : skinny_wring(wring_req);
+  const auto* wpp = ops.ptr<Bf16>(w_packed, "w_packed", true, (long)N * K);
   if (cnt.has_value() && ksplit > 1 && plan.v2) {
     TORCH_CHECK(!defer_combine, "cnt and defer_combine exclude each other");
     TORCH_CHECK(cnt->numel() >= N / 64, "cnt must be int32 of >= N/64 entries");
     // combine inside the launch: 1-D grid, tile = id / ksplit after the remap
     dispatch_mtile(M, [&](auto mt) {
       launch_skinny_v2<decltype(mt)::value, 2>(
-          wring, dim3((N / 64) * ksplit), ap, wp, rp, bp, cp, part.p, M, N, K,
-          kchunk, ksplit, nwp, (float)eps, norm_mode, ssinp, nstripes, ssoutp,
-          cntp);
+          wring, false, dim3((N / 64) * ksplit), ap, wp, rp, bp, cp, part.p, M,
+          N, K, kchunk, ksplit, nwp, (float)eps, norm_mode, ssinp, nstripes,
+          ssoutp, cntp);
     });
     return C;
   }
   dim3 grid(N / 64, ksplit);
+  const bool packed = wpp && wring == 2;
   dispatch_mtile(M, [&](auto mt) {
     if (plan.v2)
       launch_skinny_v2<decltype(mt)::value, 0>(
-          wring, grid, ap, wp, ksplit == 1 ? rp : nullptr,
+          wring, packed, grid, ap, packed ? wpp : wp,
+          ksplit == 1 ? rp : nullptr,
           ksplit == 1 ? bp : nullptr, cp, part.p, M, N, K, kchunk, ksplit, nwp,
           (float)eps, norm_mode, ssinp, nstripes,
           ksplit == 1 ? ssoutp : nullptr, (int*)nullptr);
@@ -1357,7 +1373,9 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
 // swiglu(gemm_skinny(A, W, ...)).
 torch::Tensor gemm_skinny_swiglu(torch::Tensor A, torch::Tensor W, double eps,
                                  c10::optional<torch::Tensor> ss_in,
-                                 long norm_mode_req, long wring_req) {
+                                 long norm_mode_req, long wring_req,
+                                 c10::optional<torch::Tensor> w_packed) {
+  // w_packed: W pre-tiled under the SwiGLU row map, streamed at depth 2
   Operands ops(A, "A");
   const auto* ap = ops.ptr<Bf16>(A, "A");
   const auto* wp = ops.ptr<Bf16>(W, "W");
@@ -1380,9 +1398,12 @@ torch::Tensor gemm_skinny_swiglu(torch::Tensor A, torch::Tensor W, double eps,
   auto C = torch::empty(sizes, A.options());
   auto* cp = ops.ptr<Bf16>(C, "C");
   const int wring = skinny_wring(wring_req);
+  const auto* wpp = ops.ptr<Bf16>(w_packed, "w_packed", true, (long)N * K);
+  const bool packed = wpp && wring == 2;
   dispatch_mtile(M, [&](auto mt) {
     launch_skinny_v2<decltype(mt)::value, 1>(
-        wring, dim3(I / 32), ap, wp, (const unsigned short*)nullptr,
+        wring, packed, dim3(I / 32), ap, packed ? wpp : wp,
+        (const unsigned short*)nullptr,
         (const unsigned short*)nullptr, cp, (float*)nullptr, M, N, K, K, 1,
         (const unsigned short*)nullptr, (float)eps, norm_mode, ssinp, nstripes,
         (float*)nullptr, (int*)nullptr);
@@ -1490,10 +1511,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eps") = 0.0, py::arg("ss_in") = c10::nullopt,
         py::arg("ss_out") = c10::nullopt, py::arg("norm_mode") = 0,
         py::arg("defer_combine") = false, py::arg("cnt") = c10::nullopt,
-        py::arg("wring") = 0);
+        py::arg("wring") = 0, py::arg("w_packed") = c10::nullopt);
   m.def("gemm_skinny_swiglu", &gemm_skinny_swiglu, py::arg("A"), py::arg("W"),
         py::arg("eps") = 0.0, py::arg("ss_in") = c10::nullopt,
-        py::arg("norm_mode") = 0, py::arg("wring") = 0);
+        py::arg("norm_mode") = 0, py::arg("wring") = 0,
+        py::arg("w_packed") = c10::nullopt);
   m.def("gemm_skinny_plan", &gemm_skinny_plan);
   m.def("gemm_skinny_wring_plan", &gemm_skinny_wring_plan, py::arg("N"),
         py::arg("K"), py::arg("ksplit") = 0, py::arg("wring") = 0);

@@ -191,6 +191,15 @@ DEVINL void gemm_skinny_combine_lane(
 // ring). Per accumulator the MFMA order is k ascending in steps of 32 at
 // every DEPTH, so all depths produce the same bits. Norm mode 1 exists at
 // DEPTH 2 only (the host never launches the ring with it).
+//
+// PACKED (DEPTH 2 only): W is the pre-tiled copy of common.h's
+// skinny_packed_offset — one 1 KB lane-linear block per (16-row group,
+// 32-k slice), a wave's blocks consecutive in k. A wave load is then one
+// contiguous 1 KB instead of 16 rows x 64 B at a 2K-byte stride, a set is
+// 4 KB and the wave's whole stream one contiguous run; the block base is
+// wave-uniform (scalar registers) and the lanes add lane * 16 bytes. Every
+// lane receives the very 8 elements the row-major expression gives it, so
+// the MFMA operands, their order and the outputs are bit-identical.
 template <int I>
 struct WringIdx {
   static constexpr int value = I;
@@ -205,10 +214,10 @@ DEVINL void wring_tail_dispatch(int nrem, F& f) {
   }
 }
 
-template <int MT, int EPI, int DEPTH>
+template <int MT, int EPI, int DEPTH, bool PACKED = false>
 DEVINL void gemm_skinny_v2_body(
     const unsigned short* __restrict__ A,   // (M, K) bf16
-    const unsigned short* __restrict__ W,   // (N, K) bf16
+    const unsigned short* __restrict__ W,   // (N, K) bf16, or its packed copy
     const unsigned short* __restrict__ R,   // (M, N) bf16 residual or null
     const unsigned short* __restrict__ bias,  // (N,) bf16 or null
     unsigned short* __restrict__ C,         // (M, N) bf16   (ksplit == 1)
@@ -224,6 +233,8 @@ DEVINL void gemm_skinny_v2_body(
     float* __restrict__ ssout,        // (N/64, 32) this GEMM's row sum-sq
     int* cnt) {             // EPI 2: (N/64,) tickets, zero on entry
   static_assert(DEPTH == 2 || DEPTH % 4 == 0, "ring: whole waves per A row");
+  static_assert(!PACKED || (DEPTH == 2 && EPI != 2),
+                "packed W: depth 2, plain and SwiGLU epilogues only");
   constexpr int U = 4;                     // k-slices per pipeline set (128 k)
   constexpr int KSTEP = DEPTH * 128;       // A elements staged per stage
   constexpr int RSTRIDE = KSTEP + 8;       // padded LDS row stride (elements)
@@ -267,6 +278,12 @@ DEVINL void gemm_skinny_v2_body(
   const unsigned short* wrow = W + (long)(n0 + li) * K;
   if constexpr (EPI == 1)
     wrow = W + ((long)(li < 8 ? 0 : N / 2 - 8) + tile * 32 + wave * 8 + li) * K;
+  // PACKED: the wave's group is tile * 4 + wave under both row maps; its
+  // blocks start at skinny_packed_offset(group, 0, K) and follow in k.
+  if constexpr (PACKED)
+    wrow = W + skinny_packed_offset(
+                   tile * 4 + __builtin_amdgcn_readfirstlane(wave), 0, K) +
+           lane * 8;
 
   f32x4 acc[MT];
 #pragma unroll
@@ -324,17 +341,22 @@ DEVINL void gemm_skinny_v2_body(
   };
 
   bf16x8 bB0[U], bB1[U];
+  // slice u of the DEPTH 2 set at k: where this lane's 8 elements are
+  auto wptr = [&](int k, int u) -> const unsigned short* {
+    if constexpr (PACKED) return wrow + (k / 32 + u) * SKINNY_PACK_BLOCK;
+    else return wrow + k + u * 32 + hi * 8;
+  };
   auto issue0 = [&](int k) {
 #pragma unroll
     for (int u = 0; u < U; ++u)
       bB0[u] = as_bf16x8(
-          *reinterpret_cast<const short8*>(wrow + k + u * 32 + hi * 8));
+          *reinterpret_cast<const short8*>(wptr(k, u)));
   };
   auto issue1 = [&](int k) {
 #pragma unroll
     for (int u = 0; u < U; ++u)
       bB1[u] = as_bf16x8(
-          *reinterpret_cast<const short8*>(wrow + k + u * 32 + hi * 8));
+          *reinterpret_cast<const short8*>(wptr(k, u)));
   };
   // A fragment for m-tile t, k-slice u of 128-k set `half` of the stage:
   // ds_read_b128 at row (t*16 + li), element (half*128 + u*32 + hi*8) — the
@@ -657,9 +679,9 @@ DEVINL void gemm_skinny_v2_body(
   A, W, R, bias, C, Cpart, M, N, K, kchunk, ksplit, nw, eps, norm_mode, ssin, \
       nstripes, ssout, cnt
 
-template <int MT, int EPI = 0>
+template <int MT, int EPI = 0, bool PACKED = false>
 __global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(SKINNY_V2_PARAMS) {
-  gemm_skinny_v2_body<MT, EPI, 2>(SKINNY_V2_ARGS);
+  gemm_skinny_v2_body<MT, EPI, 2, PACKED>(SKINNY_V2_ARGS);
 }
 
 template <int MT, int EPI, int DEPTH>

@@ -358,7 +358,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = 
            ss_in: Optional[torch.Tensor] = None,
            ss_out: Optional[torch.Tensor] = None,
            defer_combine: bool = False,
-           cnt: Optional[torch.Tensor] = None) -> torch.Tensor:
+           cnt: Optional[torch.Tensor] = None,
+           w_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = (rmsnorm(x) if norm else x) @ w^T (+bias) (+residual).
     Decode-shaped GEMMs (<=32 rows) on GPU go through the skinny-M MFMA
     kernel (gemm_skinny.hip) — hipBLASLt leaves ~2x weight-stream bandwidth
@@ -373,7 +374,10 @@ def linear(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = 
     K, return its f32 slabs (ksplit, M, N) WITHOUT bias instead of y, for
     rope_kv_write_part to fold; an unsplit GEMM still returns y (bf16).
     cnt (callers gate on inlaunch_combine_ok): int32 zeros, >= N/64 entries —
-    a split-K GEMM combines inside its own launch and leaves them zero."""
+    a split-K GEMM combines inside its own launch and leaves them zero.
+    w_packed: pack_skinny_w(w), the same weight in the order the skinny
+    kernel reads it (same bits out); used on the skinny path only, every
+    other path ignores it and reads w."""
     M = x.numel() // x.shape[-1]
     N, K = w.shape[0], x.shape[-1]
     # All decode-shaped GEMMs route to the skinny kernel: although hipBLASLt
@@ -396,7 +400,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = 
         return hip_ops.gemm_skinny(x.contiguous(), w, residual, bias,
                                    _INLAUNCH_KSPLIT if cnt is not None else 0,
                                    nw, eps, ss_in if norm is not None else None,
-                                   ss_out, mode, defer_combine, cnt)
+                                   ss_out, mode, defer_combine, cnt, 0,
+                                   w_packed)
     if defer_combine or cnt is not None:
         raise RuntimeError("defer_combine / cnt require the GPU skinny-GEMM "
                            "path (callers gate on fuse_norm_linear_ok)")
@@ -483,12 +488,16 @@ def inlaunch_combine_ok(x: torch.Tensor, w: torch.Tensor, which: str) -> bool:
 
 def linear_swiglu(x: torch.Tensor, gate_up_w: torch.Tensor,
                   norm: Optional[tuple] = None,
-                  ss_in: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  ss_in: Optional[torch.Tensor] = None,
+                  w_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
     """act = swiglu((rmsnorm(x) if norm else x) @ gate_up_w^T), gate_up_w the
     fused gate|up weight (2I, K) in its usual layout. Decode shapes on GPU
     run the gate_up GEMM with SwiGLU in its epilogue (one launch, the (M, 2I)
     intermediate never reaches memory); bit-identical to swiglu(linear(...)).
-    norm is (None, eps): the weight is pre-folded into gate_up_w."""
+    norm is (None, eps): the weight is pre-folded into gate_up_w.
+    w_packed: pack_skinny_w(gate_up_w, swiglu=True), used by the fused kernel
+    only (the fallback's plain GEMM pairs rows differently and reads
+    gate_up_w)."""
     if fuse_swiglu_ok(x, gate_up_w):
         _require_ext()
         assert norm is None or norm[0] is None, \
@@ -496,8 +505,17 @@ def linear_swiglu(x: torch.Tensor, gate_up_w: torch.Tensor,
         return hip_ops.gemm_skinny_swiglu(
             x.contiguous(), gate_up_w,
             float(norm[1]) if norm is not None else 0.0, ss_in,
-            2 if norm is not None else 0)
+            2 if norm is not None else 0, 0, w_packed)
     return swiglu(linear(x, gate_up_w, norm=norm, ss_in=ss_in))
+
+
+def pack_skinny_w(w: torch.Tensor, swiglu: bool = False) -> torch.Tensor:
+    """The copy of w (N, K) that linear(w_packed=...) streams, or with
+    swiglu=True the one linear_swiglu(w_packed=...) does: 1 KB blocks in the
+    skinny kernel's read order (ops/hip/common.h, skinny_packed_offset; the
+    layout is defined once more in reference.pack_skinny_w, which this is).
+    Runs once per weight, as torch index expressions on w's device."""
+    return ref.pack_skinny_w(w, swiglu)
 
 
 # mixed-device decode on the GPU: device segment on the MFMA decode kernel

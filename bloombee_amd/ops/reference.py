@@ -519,6 +519,43 @@ def moe_gemm_grouped_w4(A: torch.Tensor, packed: torch.Tensor,
     return moe_gemm_grouped(A, W, off, rowmap, slot_scale, S)
 
 
+def skinny_rowmap(N: int, swiglu: bool = False,
+                  device=None) -> torch.Tensor:
+    """Row of W that position g*16 + li of the packed skinny-GEMM weight
+    holds (ops/hip/common.h, skinny_packed_offset). Plain kernel: identity.
+    SwiGLU kernel (W the fused gate|up (2I, K), group g = tile*4 + wave):
+    gate rows g*8 + li for li < 8, up rows I + g*8 + (li - 8) otherwise."""
+    p = torch.arange(N, device=device)
+    if not swiglu:
+        return p
+    g, li = p // 16, p % 16
+    return torch.where(li < 8, g * 8 + li, N // 2 + g * 8 + li - 8)
+
+
+def pack_skinny_w(w: torch.Tensor, swiglu: bool = False) -> torch.Tensor:
+    """W (N, K) -> Wp[g][kb][hi][li][e] = W[rowmap(g*16 + li)][kb*32 + hi*8
+    + e], shape (N/16, K/32, 4, 16, 8): the order gemm_skinny_v2_kernel's
+    lanes read it in, one contiguous 1 KB block per wave load."""
+    N, K = w.shape
+    assert N % 16 == 0 and K % 32 == 0, "packed skinny W needs N%16, K%32"
+    assert not swiglu or N % 64 == 0, "SwiGLU row map needs I % 32 == 0"
+    rows = w[skinny_rowmap(N, True, w.device)] if swiglu else w
+    return (rows.reshape(N // 16, 16, K // 32, 4, 8)   # [g, li, kb, hi, e]
+            .permute(0, 2, 3, 1, 4).contiguous())
+
+
+def unpack_skinny_w(wp: torch.Tensor, swiglu: bool = False) -> torch.Tensor:
+    """Inverse of pack_skinny_w."""
+    G, KB = wp.shape[0], wp.shape[1]
+    N, K = G * 16, KB * 32
+    rows = wp.permute(0, 3, 1, 2, 4).reshape(N, K)
+    if not swiglu:
+        return rows.contiguous()
+    w = torch.empty_like(rows)
+    w[skinny_rowmap(N, True, wp.device)] = rows
+    return w
+
+
 def attn_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
                window: int = 0,
                alibi_slopes: Optional[torch.Tensor] = None) -> torch.Tensor:
