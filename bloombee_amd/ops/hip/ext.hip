@@ -235,23 +235,78 @@ static int skinny_wring(long req) {
   return (int)req;
 }
 
+// Cache policy of the v2 kernel's W loads (its NT flag): nontemporal or the
+// default. BBAMD_W_NT = "auto" (default) / "0" / "1" sets it for the process,
+// a call's w_nt request (1: nt, -1: plain, 0: follow the process) for one
+// call. "auto" is nt for exactly the (N, K, packed?) streams of kWntFaster,
+// those the flagship's kernel trace showed faster with nt in every run (three
+// nt runs against four plain ones, no overlap; profiles/r09_nt_weights.md has
+// the figures and the noise floor), and plain for every other shape: packed
+// qkv was level, packed o and every row-major stream slower. As in r06 and
+// r08 a stand-alone figure does not decide for these kernels, so there is no
+// rule, only the table.
+struct WntShape {
+  long N, K;
+  bool packed;
+};
+static constexpr WntShape kWntFaster[] = {
+    {28672, 4096, true},  // gate_up, packed: 42.0 -> 40.9 us
+    {4096, 14336, true},  // down, packed: 22.5 -> 21.3 us
+};
+
+enum class WntMode { automatic, plain, nt };
+
+static WntMode parse_w_nt(const char* e) {
+  const std::string v = e ? e : "auto";
+  if (v == "auto" || v.empty()) return WntMode::automatic;
+  if (v == "0") return WntMode::plain;
+  if (v == "1") return WntMode::nt;
+  TORCH_CHECK(false, "BBAMD_W_NT must be auto, 0 or 1, got '", v, "'");
+}
+
+static bool skinny_w_nt(WntMode mode, long req, long N, long K, bool packed) {
+  TORCH_CHECK(req >= -1 && req <= 1,
+              "w_nt must be 0 (process setting), 1 (nt) or -1 (plain), got ", req);
+  if (req != 0) return req > 0;
+  if (mode != WntMode::automatic) return mode == WntMode::nt;
+  for (const WntShape& s : kWntFaster)
+    if (s.N == N && s.K == K && s.packed == packed) return true;
+  return false;
+}
+
+static bool skinny_w_nt(long req, long N, long K, bool packed) {
+  static const WntMode env = parse_w_nt(std::getenv("BBAMD_W_NT"));
+  return skinny_w_nt(env, req, N, K, packed);
+}
+
 // Launches gemm_skinny_v2_kernel<MT, EPI> (depth 2) or the ring kernel at
 // `depth`. `packed`: the W among args is the pre-tiled copy, which only the
-// depth-2 kernel with the plain or the SwiGLU epilogue reads.
-template <int MT, int EPI, typename... Args>
-static void launch_skinny_v2(int depth, bool packed, dim3 grid, Args... args) {
+// depth-2 kernel with the plain or the SwiGLU epilogue reads. `nt`: W loads
+// with the nontemporal hint.
+template <int MT, int EPI, bool NT, typename... Args>
+static void launch_skinny_v2_nt(int depth, bool packed, dim3 grid, Args... args) {
   if constexpr (EPI != 2) {
     if (packed) {
       TORCH_CHECK(depth == 2, "packed W runs at ring depth 2 only");
-      gemm_skinny_v2_kernel<MT, EPI, true><<<grid, 256, 0, cur_stream()>>>(args...);
+      gemm_skinny_v2_kernel<MT, EPI, true, NT>
+          <<<grid, 256, 0, cur_stream()>>>(args...);
       return;
     }
   }
   TORCH_CHECK(!packed, "packed W: plain and SwiGLU epilogues only");
   if (depth == 2)
-    gemm_skinny_v2_kernel<MT, EPI><<<grid, 256, 0, cur_stream()>>>(args...);
+    gemm_skinny_v2_kernel<MT, EPI, false, NT>
+        <<<grid, 256, 0, cur_stream()>>>(args...);
   else
-    gemm_skinny_v2_ring_kernel<MT, EPI, 4><<<grid, 256, 0, cur_stream()>>>(args...);
+    gemm_skinny_v2_ring_kernel<MT, EPI, 4, NT>
+        <<<grid, 256, 0, cur_stream()>>>(args...);
+}
+
+template <int MT, int EPI, typename... Args>
+static void launch_skinny_v2(int depth, bool packed, bool nt, dim3 grid,
+                             Args... args) {
+  if (nt) launch_skinny_v2_nt<MT, EPI, true>(depth, packed, grid, args...);
+  else launch_skinny_v2_nt<MT, EPI, false>(depth, packed, grid, args...);
 }
 
 struct W4Plan {
@@ -308,6 +363,24 @@ std::tuple<long, std::vector<long>> gemm_skinny_wring_plan(long N, long K,
   const std::vector<long> built(std::begin(kWringDepths), std::end(kWringDepths));
   if (!p.v2) return {0, built};
   return {skinny_wring(wring_req), built};
+}
+
+// Whether a gemm_skinny / gemm_skinny_swiglu call streams an (N, K) weight
+// (packed: from its pre-tiled copy) with nontemporal loads, given the call's
+// w_nt request and the process setting: `setting` as BBAMD_W_NT would spell
+// it, or none for what this process read from the environment. False where
+// the shape runs on the v1 kernel, which has no such flavour. With it, the
+// shapes "auto" turns on, as (N, K, packed).
+std::tuple<bool, std::vector<std::tuple<long, long, bool>>> gemm_skinny_nt_plan(
+    long N, long K, bool packed, long w_nt_req,
+    c10::optional<std::string> setting) {
+  std::vector<std::tuple<long, long, bool>> table;
+  for (const WntShape& s : kWntFaster) table.emplace_back(s.N, s.K, s.packed);
+  const bool v2 = skinny_plan(N, K, 0).v2;
+  const bool nt = setting.has_value()
+                      ? skinny_w_nt(parse_w_nt(setting->c_str()), w_nt_req, N, K, packed)
+                      : skinny_w_nt(w_nt_req, N, K, packed);
+  return {v2 && nt, table};
 }
 
 std::tuple<bool, long, long> gemm_w4_plan(long M, long N, long K, long ksplit_req) {
@@ -1260,7 +1333,7 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
                           c10::optional<torch::Tensor> ss_out,
                           long norm_mode_req, bool defer_combine,
                           c10::optional<torch::Tensor> cnt, long wring_req,
-                          c10::optional<torch::Tensor> w_packed) {
+                          c10::optional<torch::Tensor> w_packed, long w_nt_req) {
   // defer_combine: under split-K skip the combine and return the f32 slabs
   // (ksplit, M, N) for a consumer that folds them itself (rope_kv_write_part);
   // bias is then the consumer's to add. With ksplit == 1 there is nothing to
@@ -1273,6 +1346,10 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
   // w_packed: W in the pre-tiled layout of common.h (identity row map),
   // streamed instead of W where the call runs the depth-2 v2 kernel with the
   // plain epilogue; every other path reads W.
+  // w_nt: cache policy of the v2 kernel's W loads for this call
+  // (skinny_w_nt); 0 leaves it to BBAMD_W_NT and the table. The value is
+  // checked on every path; the v1 kernel (K % 256 != 0) has no nt flavour and
+  // ignores a w_nt = 1, as gemm_skinny_nt_plan reports.
   Operands ops(A, "A");
   const auto* ap = ops.ptr<Bf16>(A, "A");
   const auto* wp = ops.ptr<Bf16>(W, "W");
@@ -1319,7 +1396,8 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
     // combine inside the launch: 1-D grid, tile = id / ksplit after the remap
     dispatch_mtile(M, [&](auto mt) {
       launch_skinny_v2<decltype(mt)::value, 2>(
-          wring, false, dim3((N / 64) * ksplit), ap, wp, rp, bp, cp, part.p, M,
+          wring, false, skinny_w_nt(w_nt_req, N, K, false),
+          dim3((N / 64) * ksplit), ap, wp, rp, bp, cp, part.p, M,
           N, K, kchunk, ksplit, nwp, (float)eps, norm_mode, ssinp, nstripes,
           ssoutp, cntp);
     });
@@ -1327,10 +1405,11 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
   }
   dim3 grid(N / 64, ksplit);
   const bool packed = wpp && wring == 2;
+  const bool nt = skinny_w_nt(w_nt_req, N, K, packed);
   dispatch_mtile(M, [&](auto mt) {
     if (plan.v2)
       launch_skinny_v2<decltype(mt)::value, 0>(
-          wring, packed, grid, ap, packed ? wpp : wp,
+          wring, packed, nt, grid, ap, packed ? wpp : wp,
           ksplit == 1 ? rp : nullptr,
           ksplit == 1 ? bp : nullptr, cp, part.p, M, N, K, kchunk, ksplit, nwp,
           (float)eps, norm_mode, ssinp, nstripes,
@@ -1374,8 +1453,10 @@ torch::Tensor gemm_skinny(torch::Tensor A, torch::Tensor W,
 torch::Tensor gemm_skinny_swiglu(torch::Tensor A, torch::Tensor W, double eps,
                                  c10::optional<torch::Tensor> ss_in,
                                  long norm_mode_req, long wring_req,
-                                 c10::optional<torch::Tensor> w_packed) {
+                                 c10::optional<torch::Tensor> w_packed,
+                                 long w_nt_req) {
   // w_packed: W pre-tiled under the SwiGLU row map, streamed at depth 2
+  // w_nt: as for gemm_skinny
   Operands ops(A, "A");
   const auto* ap = ops.ptr<Bf16>(A, "A");
   const auto* wp = ops.ptr<Bf16>(W, "W");
@@ -1400,9 +1481,10 @@ torch::Tensor gemm_skinny_swiglu(torch::Tensor A, torch::Tensor W, double eps,
   const int wring = skinny_wring(wring_req);
   const auto* wpp = ops.ptr<Bf16>(w_packed, "w_packed", true, (long)N * K);
   const bool packed = wpp && wring == 2;
+  const bool nt = skinny_w_nt(w_nt_req, N, K, packed);
   dispatch_mtile(M, [&](auto mt) {
     launch_skinny_v2<decltype(mt)::value, 1>(
-        wring, packed, dim3(I / 32), ap, packed ? wpp : wp,
+        wring, packed, nt, dim3(I / 32), ap, packed ? wpp : wp,
         (const unsigned short*)nullptr,
         (const unsigned short*)nullptr, cp, (float*)nullptr, M, N, K, K, 1,
         (const unsigned short*)nullptr, (float)eps, norm_mode, ssinp, nstripes,
@@ -1511,12 +1593,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eps") = 0.0, py::arg("ss_in") = c10::nullopt,
         py::arg("ss_out") = c10::nullopt, py::arg("norm_mode") = 0,
         py::arg("defer_combine") = false, py::arg("cnt") = c10::nullopt,
-        py::arg("wring") = 0, py::arg("w_packed") = c10::nullopt);
+        py::arg("wring") = 0, py::arg("w_packed") = c10::nullopt,
+        py::arg("w_nt") = 0);
   m.def("gemm_skinny_swiglu", &gemm_skinny_swiglu, py::arg("A"), py::arg("W"),
         py::arg("eps") = 0.0, py::arg("ss_in") = c10::nullopt,
         py::arg("norm_mode") = 0, py::arg("wring") = 0,
-        py::arg("w_packed") = c10::nullopt);
+        py::arg("w_packed") = c10::nullopt, py::arg("w_nt") = 0);
   m.def("gemm_skinny_plan", &gemm_skinny_plan);
+  m.def("gemm_skinny_nt_plan", &gemm_skinny_nt_plan, py::arg("N"), py::arg("K"),
+        py::arg("packed") = false, py::arg("w_nt") = 0,
+        py::arg("setting") = c10::nullopt);
   m.def("gemm_skinny_wring_plan", &gemm_skinny_wring_plan, py::arg("N"),
         py::arg("K"), py::arg("ksplit") = 0, py::arg("wring") = 0);
   m.def("rope_kv_write_part", &rope_kv_write_part);

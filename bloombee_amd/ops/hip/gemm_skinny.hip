@@ -200,6 +200,13 @@ DEVINL void gemm_skinny_combine_lane(
 // wave-uniform (scalar registers) and the lanes add lane * 16 bytes. Every
 // lane receives the very 8 elements the row-major expression gives it, so
 // the MFMA operands, their order and the outputs are bit-identical.
+//
+// NT: the W loads (issue0 / issue1, the ring's issue) carry the nontemporal
+// hint, as the decode attention kernel's K/V loads do: W is read once, and
+// the lines every workgroup re-reads (A, ssin, R, the split-K slabs) should
+// not be evicted by it. Only the cache policy bit of those loads differs; A
+// staging, nw, ssin, R, bias, the slab loads and every store keep the default
+// policy. NT = false is the kernel as it was.
 template <int I>
 struct WringIdx {
   static constexpr int value = I;
@@ -214,7 +221,7 @@ DEVINL void wring_tail_dispatch(int nrem, F& f) {
   }
 }
 
-template <int MT, int EPI, int DEPTH, bool PACKED = false>
+template <int MT, int EPI, int DEPTH, bool PACKED = false, bool NT = false>
 DEVINL void gemm_skinny_v2_body(
     const unsigned short* __restrict__ A,   // (M, K) bf16
     const unsigned short* __restrict__ W,   // (N, K) bf16, or its packed copy
@@ -254,18 +261,8 @@ DEVINL void gemm_skinny_v2_body(
   const int lane = threadIdx.x & (WAVE - 1);
   const int li = lane & 15;
   const int hi = lane >> 4;
-  // Bijective XCD-aware remap: the dispatcher places block b on XCD b%8, so
-  // without the remap memory-adjacent N-tiles land on different XCDs. Group
-  // them instead: each XCD streams one contiguous W region (guide: +10-12%
-  // when HBM-bound).
-  int tile = blockIdx.x;
-  {
-    const int nwg = gridDim.x;
-    const int xcd = tile % 8, orig8 = tile / 8;
-    const int q = nwg / 8, r = nwg % 8;
-    if (nwg >= 8)
-      tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig8;
-  }
+  // each XCD streams one contiguous W region (common.h)
+  int tile = xcd_remap(blockIdx.x, gridDim.x);
   int split = blockIdx.y;
   if constexpr (EPI == 2) {
     split = tile % ksplit;
@@ -341,6 +338,13 @@ DEVINL void gemm_skinny_v2_body(
   };
 
   bf16x8 bB0[U], bB1[U];
+  // one 16 B piece of the W stream
+  auto load_w = [&](const unsigned short* p) -> short8 {
+    if constexpr (NT)
+      return __builtin_nontemporal_load(reinterpret_cast<const short8*>(p));
+    else
+      return *reinterpret_cast<const short8*>(p);
+  };
   // slice u of the DEPTH 2 set at k: where this lane's 8 elements are
   auto wptr = [&](int k, int u) -> const unsigned short* {
     if constexpr (PACKED) return wrow + (k / 32 + u) * SKINNY_PACK_BLOCK;
@@ -349,14 +353,12 @@ DEVINL void gemm_skinny_v2_body(
   auto issue0 = [&](int k) {
 #pragma unroll
     for (int u = 0; u < U; ++u)
-      bB0[u] = as_bf16x8(
-          *reinterpret_cast<const short8*>(wptr(k, u)));
+      bB0[u] = as_bf16x8(load_w(wptr(k, u)));
   };
   auto issue1 = [&](int k) {
 #pragma unroll
     for (int u = 0; u < U; ++u)
-      bB1[u] = as_bf16x8(
-          *reinterpret_cast<const short8*>(wptr(k, u)));
+      bB1[u] = as_bf16x8(load_w(wptr(k, u)));
   };
   // A fragment for m-tile t, k-slice u of 128-k set `half` of the stage:
   // ds_read_b128 at row (t*16 + li), element (half*128 + u*32 + hi*8) — the
@@ -460,8 +462,7 @@ DEVINL void gemm_skinny_v2_body(
     auto issue = [&](int j, int k) {
 #pragma unroll
       for (int u = 0; u < U; ++u)
-        ring[j][u] = as_bf16x8(
-            *reinterpret_cast<const short8*>(wrow + k + u * 32 + hi * 8));
+        ring[j][u] = as_bf16x8(load_w(wrow + k + u * 32 + hi * 8));
     };
     // A stream shorter than the ring re-reads its last set into the spare
     // registers: every request stays unconditional.
@@ -679,15 +680,15 @@ DEVINL void gemm_skinny_v2_body(
   A, W, R, bias, C, Cpart, M, N, K, kchunk, ksplit, nw, eps, norm_mode, ssin, \
       nstripes, ssout, cnt
 
-template <int MT, int EPI = 0, bool PACKED = false>
+template <int MT, int EPI = 0, bool PACKED = false, bool NT = false>
 __global__ __launch_bounds__(256) void gemm_skinny_v2_kernel(SKINNY_V2_PARAMS) {
-  gemm_skinny_v2_body<MT, EPI, 2, PACKED>(SKINNY_V2_ARGS);
+  gemm_skinny_v2_body<MT, EPI, 2, PACKED, NT>(SKINNY_V2_ARGS);
 }
 
-template <int MT, int EPI, int DEPTH>
+template <int MT, int EPI, int DEPTH, bool NT = false>
 __global__ __launch_bounds__(256, 3) void gemm_skinny_v2_ring_kernel(
     SKINNY_V2_PARAMS) {
-  gemm_skinny_v2_body<MT, EPI, DEPTH>(SKINNY_V2_ARGS);
+  gemm_skinny_v2_body<MT, EPI, DEPTH, false, NT>(SKINNY_V2_ARGS);
 }
 
 // Split-K combine that also emits per-stripe row sum-of-squares (ssout
@@ -703,6 +704,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_combine_ss_kernel(
   const int lane = threadIdx.x & (WAVE - 1);
   const int m = blockIdx.y * 16 + (threadIdx.x >> 6) * 4 + (lane >> 4);
   if (m >= M) return;
+  // the plain index on purpose, not xcd_remap (profiles/r09_nt_weights.md)
   gemm_skinny_combine_lane(Cpart, R, bias, C, ssout, M, N, ksplit, blockIdx.x,
                            m, lane);
 }

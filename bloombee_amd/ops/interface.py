@@ -359,7 +359,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = 
            ss_out: Optional[torch.Tensor] = None,
            defer_combine: bool = False,
            cnt: Optional[torch.Tensor] = None,
-           w_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+           w_packed: Optional[torch.Tensor] = None,
+           w_nt: int = 0) -> torch.Tensor:
     """y = (rmsnorm(x) if norm else x) @ w^T (+bias) (+residual).
     Decode-shaped GEMMs (<=32 rows) on GPU go through the skinny-M MFMA
     kernel (gemm_skinny.hip) — hipBLASLt leaves ~2x weight-stream bandwidth
@@ -377,9 +378,13 @@ def linear(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = 
     a split-K GEMM combines inside its own launch and leaves them zero.
     w_packed: pack_skinny_w(w), the same weight in the order the skinny
     kernel reads it (same bits out); used on the skinny path only, every
-    other path ignores it and reads w."""
+    other path ignores it and reads w.
+    w_nt: cache policy of the skinny kernel's weight loads for this call, 1
+    nontemporal, -1 default, 0 what BBAMD_W_NT says (same bits out)."""
     M = x.numel() // x.shape[-1]
     N, K = w.shape[0], x.shape[-1]
+    if w_nt not in (-1, 0, 1):    # on every path, also those that ignore it
+        raise RuntimeError(f"w_nt must be 0, 1 or -1, got {w_nt}")
     # All decode-shaped GEMMs route to the skinny kernel: although hipBLASLt
     # wins the two MLP shapes in an isolated microbench, in the real decode
     # step it runs ~1.5x slower (cold L2 / per-stream heuristics, see
@@ -401,7 +406,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = 
                                    _INLAUNCH_KSPLIT if cnt is not None else 0,
                                    nw, eps, ss_in if norm is not None else None,
                                    ss_out, mode, defer_combine, cnt, 0,
-                                   w_packed)
+                                   w_packed, w_nt)
     if defer_combine or cnt is not None:
         raise RuntimeError("defer_combine / cnt require the GPU skinny-GEMM "
                            "path (callers gate on fuse_norm_linear_ok)")
@@ -489,7 +494,8 @@ def inlaunch_combine_ok(x: torch.Tensor, w: torch.Tensor, which: str) -> bool:
 def linear_swiglu(x: torch.Tensor, gate_up_w: torch.Tensor,
                   norm: Optional[tuple] = None,
                   ss_in: Optional[torch.Tensor] = None,
-                  w_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  w_packed: Optional[torch.Tensor] = None,
+                  w_nt: int = 0) -> torch.Tensor:
     """act = swiglu((rmsnorm(x) if norm else x) @ gate_up_w^T), gate_up_w the
     fused gate|up weight (2I, K) in its usual layout. Decode shapes on GPU
     run the gate_up GEMM with SwiGLU in its epilogue (one launch, the (M, 2I)
@@ -497,7 +503,9 @@ def linear_swiglu(x: torch.Tensor, gate_up_w: torch.Tensor,
     norm is (None, eps): the weight is pre-folded into gate_up_w.
     w_packed: pack_skinny_w(gate_up_w, swiglu=True), used by the fused kernel
     only (the fallback's plain GEMM pairs rows differently and reads
-    gate_up_w)."""
+    gate_up_w). w_nt: as for linear."""
+    if w_nt not in (-1, 0, 1):
+        raise RuntimeError(f"w_nt must be 0, 1 or -1, got {w_nt}")
     if fuse_swiglu_ok(x, gate_up_w):
         _require_ext()
         assert norm is None or norm[0] is None, \
@@ -505,8 +513,8 @@ def linear_swiglu(x: torch.Tensor, gate_up_w: torch.Tensor,
         return hip_ops.gemm_skinny_swiglu(
             x.contiguous(), gate_up_w,
             float(norm[1]) if norm is not None else 0.0, ss_in,
-            2 if norm is not None else 0, 0, w_packed)
-    return swiglu(linear(x, gate_up_w, norm=norm, ss_in=ss_in))
+            2 if norm is not None else 0, 0, w_packed, w_nt)
+    return swiglu(linear(x, gate_up_w, norm=norm, ss_in=ss_in, w_nt=w_nt))
 
 
 def pack_skinny_w(w: torch.Tensor, swiglu: bool = False) -> torch.Tensor:

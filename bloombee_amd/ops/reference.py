@@ -556,6 +556,17 @@ def unpack_skinny_w(wp: torch.Tensor, swiglu: bool = False) -> torch.Tensor:
     return w
 
 
+def xcd_remap(b: int, nwg: int) -> int:
+    """Tile that block b of a grid row of nwg blocks works on (ops/hip/
+    common.h, xcd_remap): the dispatcher puts block b on XCD b % 8, the remap
+    gives each XCD one contiguous run of tiles (the skinny GEMM's W region)."""
+    if nwg < 8:
+        return b
+    xcd, orig8 = b % 8, b // 8
+    q, r = divmod(nwg, 8)
+    return (xcd * (q + 1) if xcd < r else r * (q + 1) + (xcd - r) * q) + orig8
+
+
 def attn_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
                window: int = 0,
                alibi_slopes: Optional[torch.Tensor] = None) -> torch.Tensor:
