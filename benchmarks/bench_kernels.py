@@ -435,6 +435,63 @@ def bench_moe_w4():
             del w4s, wbs
 
 
+def bench_w4_tiled():
+    """gemm_w4 above 32 rows (w4_gemm_tiled.hip) beside the path it replaces
+    in linear_w4 (quant4_unpack + F.linear + residual add, what
+    BBAMD_W4_TILED=0 runs) on the same inputs, at the llama-3-8b projections
+    and M = 33..1024. Three alternating rounds per point (median and
+    spread). Both paths cycle through enough copies of the codes that a call
+    never finds them in the 256 MB last-level cache. TB/s is codes + scale +
+    zero over the kernel's time, TF/s is 2 M N K over it; `plan` is (BM,
+    ksplit, kchunk) from gemm_w4_tiled_plan. BBAMD_BENCH_W4_KSPLIT="1,2,4"
+    adds the kernel's time at those forced splits."""
+    forced = [int(s) for s in os.environ.get("BBAMD_BENCH_W4_KSPLIT", "").split(",") if s]
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    for N, K, tag in [(6144, 4096, "qkv"), (4096, 4096, "o"),
+                      (28672, 4096, "gate_up"), (4096, 14336, "down")]:
+        wb = torch.randn(N, K, generator=gen, device=DEV,
+                         dtype=torch.float32).mul_(K ** -0.5).to(torch.bfloat16)
+        packed, scale, zero = ops.quant4_pack(wb)
+        del wb
+        w4_bytes = N * K // 2 + 4 * N * K // 64
+        nrot = max(2, -(-(512 << 20) // w4_bytes))
+        ws = [(packed.clone(), scale.clone(), zero.clone()) for _ in range(nrot)]
+        for M in (33, 48, 64, 96, 128, 192, 256, 384, 512, 1024):
+            a = torch.randn(M, K, generator=gen, device=DEV,
+                            dtype=torch.float32).to(torch.bfloat16)
+            r = torch.randn(M, N, generator=gen, device=DEV,
+                            dtype=torch.float32).to(torch.bfloat16)
+            i = [0]
+
+            def kernel(ks=0):
+                p, s, z = ws[i[0] % nrot]
+                i[0] += 1
+                return ops.hip_ops.gemm_w4(a, p.view(N, K // 2), s.view(N, K // 64),
+                                           z.view(N, K // 64), r, None, N, ks)
+
+            def parent():
+                p, s, z = ws[i[0] % nrot]
+                i[0] += 1
+                w = ops.quant4_unpack(p.view(-1, 32), s.view(-1), z.view(-1)).view(N, K)
+                return torch.nn.functional.linear(a, w) + r
+
+            tk, tp = [], []
+            for _ in range(3):
+                tk.append(_event_time(kernel, 20, 5))
+                tp.append(_event_time(parent, 20, 5))
+            tk.sort(), tp.sort()
+            extra = "".join(
+                f"  ks={ks} {_event_time(lambda: kernel(ks), 20, 5)*1e6:.1f} us"
+                for ks in forced)
+            plan = tuple(ops.hip_ops.gemm_w4_tiled_plan(M, N, K, 0))
+            print(f"w4_tiled {tag} N{N} K{K} M{M} plan {plan}: "
+                  f"kernel {tk[1]*1e6:7.1f} us [{tk[0]*1e6:.1f}..{tk[2]*1e6:.1f}] "
+                  f"{w4_bytes/tk[1]/1e12:5.2f} TB/s {2.0*M*N*K/tk[1]/1e12:6.1f} TF/s   "
+                  f"unpack+library {tp[1]*1e6:7.1f} us [{tp[0]*1e6:.1f}..{tp[2]*1e6:.1f}]   "
+                  f"parent/kernel {tp[1]/tk[1]:5.2f}{extra}", flush=True)
+        del ws
+
+
 ALL = {
     "attn_decode": bench_attn_decode,
     "attn_mixed": bench_attn_mixed,
@@ -448,6 +505,7 @@ ALL = {
     "gemm": bench_gemm,
     "gemm_norm": bench_gemm_norm,
     "moe_w4": bench_moe_w4,
+    "w4_tiled": bench_w4_tiled,
 }
 
 if __name__ == "__main__":

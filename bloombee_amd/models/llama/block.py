@@ -195,8 +195,10 @@ class LlamaBlock(FamilyBlock):
         through w4_gemm.hip (FlexGen-style compression ON the compute
         path — the reference only compresses weights at rest,
         flexgen_utils/compression.py:94-210). keep_full=False drops the
-        bf16 weights (4x memory; the block becomes inference-only and
-        prefill-shaped GEMMs dequantize on the fly)."""
+        bf16 weights (4x memory; the block becomes inference-only). Up to
+        512 rows the GEMMs read the codes directly (w4_gemm.hip to 32
+        rows, w4_gemm_tiled.hip above); larger prefill-shaped GEMMs
+        dequantize the weight on the fly (ops.linear_w4)."""
         self._drop_packed()
         pack_q4(self, ("qkv_w", "o_w", "gate_up_w", "down_w"), keep_full)
         return self

@@ -22,6 +22,7 @@
 #include "moe_gemm.hip"
 #include "w4_gemm.hip"
 #include "moe_gemm_w4.hip"
+#include "w4_gemm_tiled.hip"
 #include "mfma_selftest.hip"
 #include "quant4.hip"
 #include "wire.h"
@@ -335,6 +336,29 @@ static W4Plan w4_plan(long M, long N, long K, long ksplit_req) {
   return {false, s.ksplit, s.kchunk};
 }
 
+// gemm_w4 above 32 rows (w4_gemm_tiled.hip): block tile BM x 128.
+struct W4TiledPlan {
+  int BM, ksplit, kchunk;
+};
+
+static W4TiledPlan w4_tiled_plan(long M, long N, long K, long ksplit_req) {
+  TORCH_CHECK(N >= 64 && K >= 128 && K % 128 == 0 && N % 64 == 0,
+              "K%128, N%64 required");
+  TORCH_CHECK(M > 32, "the tiled W4 kernel is for M > 32, got ", M);
+  // the smaller tile where it cuts padded rows (M 33..64, 129..192, ...)
+  const int BM = (M + 127) / 128 * 128 <= (M + 63) / 64 * 64 ? 128 : 64;
+  int ksplit = (int)ksplit_req;
+  if (ksplit <= 0) {
+    // two blocks per CU keep 32 KB of codes per CU in flight; beyond 8
+    // splits the f32 slabs cost more than the stream they hide
+    const long blocks = ((N + 127) / 128) * ((M + BM - 1) / BM);
+    ksplit = (int)std::max<long>(
+        1, std::min<long>(std::min<long>(8, K / 512), 512 / blocks));
+  }
+  const SplitK s = split_k_chunks((int)K, 128, ksplit);
+  return {BM, s.ksplit, s.kchunk};
+}
+
 // The W4 stream is latency-bound below ~1800 blocks, as for gemm_w4. The host
 // cannot know how many experts are active without a sync; min(E, S) bounds it.
 static SplitK moe_w4_plan(long E, long N, long K, long S, long ksplit_req) {
@@ -386,6 +410,12 @@ std::tuple<bool, std::vector<std::tuple<long, long, bool>>> gemm_skinny_nt_plan(
 std::tuple<bool, long, long> gemm_w4_plan(long M, long N, long K, long ksplit_req) {
   const W4Plan p = w4_plan(M, N, K, ksplit_req);
   return {p.gemv, p.ksplit, p.kchunk};
+}
+
+std::tuple<long, long, long> gemm_w4_tiled_plan(long M, long N, long K,
+                                                 long ksplit_req) {
+  const W4TiledPlan p = w4_tiled_plan(M, N, K, ksplit_req);
+  return {p.BM, p.ksplit, p.kchunk};
 }
 
 std::tuple<long, long> moe_gemm_w4_plan(long E, long N, long K, long S,
@@ -1248,30 +1278,57 @@ torch::Tensor moe_gemm_w4(torch::Tensor A, torch::Tensor packed,
 }
 
 
-// C(M,N) = A @ dequant4(Wq)^T [+R] [+bias], M <= 32 (w4_gemm.hip). Wq/scale/
-// zero in quant4_pack layout (2 codes/byte along K, f16 scale+zero per group
-// of 64). ~3.5x less weight-stream bytes than the bf16 kernel.
+// C(M,N) = A @ dequant4(Wq)^T [+R] [+bias]. Wq/scale/zero in quant4_pack
+// layout (2 codes/byte along K, f16 scale+zero per group of 64). ~3.5x less
+// weight-stream bytes than the bf16 kernel. M <= 32: f16 A, the GEMV / skinny
+// kernels of w4_gemm.hip. M > 32: bf16 A, the tiled kernel of
+// w4_gemm_tiled.hip, which converts A itself.
 torch::Tensor gemm_w4(torch::Tensor A, torch::Tensor Wq, torch::Tensor scale,
                       torch::Tensor zero,
                       c10::optional<torch::Tensor> residual,
                       c10::optional<torch::Tensor> bias, long N_, long ksplit_req) {
   Operands ops(A, "A");
-  // fp16 activations: the wrapper converts
-  const auto* ap = reinterpret_cast<const _Float16*>(ops.ptr<F16>(A, "A"));
   const int K = A.size(-1);
-  const int M = A.numel() / K;
+  const long M = A.numel() / K;
   const int N = (int)N_;
-  TORCH_CHECK(M <= 32, "gemm_w4 is for M <= 32, got ", M);
   const auto* qp = ops.ptr<U8>(Wq, "Wq", true, (long)N * K / 2);
   const auto* scp = ops.ptr<F16>(scale, "scale", true, (long)N * K / 64);
   const auto* zp = ops.ptr<F16>(zero, "zero", true, (long)N * K / 64);
   TORCH_CHECK(K % 128 == 0 && N % 64 == 0, "K%128, N%64 required");
-  const auto* rp = ops.ptr<Bf16>(residual, "residual", true, (long)M * N);
+  const auto* rp = ops.ptr<Bf16>(residual, "residual", true, M * N);
   const auto* bp = ops.ptr<Bf16>(bias, "bias", true, N);
   auto sizes = A.sizes().vec();
   sizes.back() = N;
   auto C = torch::empty(sizes, A.options().dtype(at::kBFloat16));
   auto* cp = ops.ptr<Bf16>(C, "C");
+  if (M > 32) {
+    TORCH_CHECK(A.scalar_type() == at::kBFloat16,
+                "gemm_w4 at M > 32 takes bf16 activations, got ", A.scalar_type());
+    const auto* abp = ops.ptr<Bf16>(A, "A");
+    const W4TiledPlan plan = w4_tiled_plan(M, N, K, ksplit_req);
+    const int ksplit = plan.ksplit;
+    const long mtiles = (M + plan.BM - 1) / plan.BM;
+    const long blocks = ((N + 127) / 128) * mtiles;
+    TORCH_CHECK(M < (1L << 31) && blocks < (1L << 31), "gemm_w4: M too large");
+    const Slabs part = alloc_slabs(ops, A, ksplit, M, N);
+    const dim3 grid((unsigned)blocks, ksplit);
+    auto launch = [&](auto bm) {
+      gemm_w4_tiled_kernel<decltype(bm)::value><<<grid, 256, 0, cur_stream()>>>(
+          abp, qp, scp, zp, ksplit == 1 ? rp : nullptr, ksplit == 1 ? bp : nullptr,
+          cp, part.p, (int)M, N, K, (int)mtiles, plan.kchunk);
+    };
+    if (plan.BM == 128) launch(std::integral_constant<int, 128>{});
+    else launch(std::integral_constant<int, 64>{});
+    if (ksplit > 1) {
+      const long total = M * N;
+      const int cgrid = (int)std::min<long>((total + 255) / 256, 2048);
+      gemm_skinny_combine_kernel<<<cgrid, 256, 0, cur_stream()>>>(
+          part.p, rp, bp, cp, (int)M, N, ksplit);
+    }
+    return C;
+  }
+  // fp16 activations: the wrapper converts
+  const auto* ap = reinterpret_cast<const _Float16*>(ops.ptr<F16>(A, "A"));
   const W4Plan plan = w4_plan(M, N, K, ksplit_req);
   if (plan.gemv) {
     const int rpw = 4;
@@ -1609,6 +1666,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gemm", &moe_gemm);
   m.def("gemm_w4", &gemm_w4);
   m.def("gemm_w4_plan", &gemm_w4_plan);
+  m.def("gemm_w4_tiled_plan", &gemm_w4_tiled_plan);
   m.def("moe_gemm_w4", &moe_gemm_w4);
   m.def("moe_gemm_w4_plan", &moe_gemm_w4_plan);
   m.def("quant4_pack", &quant4_pack);

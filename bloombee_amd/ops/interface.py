@@ -694,19 +694,42 @@ def moe_gemm_grouped_w4(A: torch.Tensor, packed: torch.Tensor,
                                    slot_scale, S)
 
 
+# Largest M linear_w4 sends to the tiled W4 kernel: the largest M of the
+# measured sweep at which it beats dequantize + library GEMM + residual add on
+# all four llama-3-8b projections (profiles/r10_w4_tiled.md): at 1024 the
+# library wins on three of them.
+_W4_TILED_MAX_M = 512
+
+
 def linear_w4(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor,
               zero: torch.Tensor, N: int,
               residual: Optional[torch.Tensor] = None,
               bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x @ dequant4(W)^T (+bias) (+residual) with W in quant4_pack
-    layout (N, K/2 codes + f16 scale/zero per 64-group). Decode shapes
-    (M<=32) run the 4-bit weight-stream kernel (w4_gemm.hip, ~3.5x less
-    HBM traffic than bf16); anything else dequantizes and uses the dense
-    path — W4 is a decode-bandwidth play, prefill is compute-bound."""
+    layout (N, K/2 codes + f16 scale/zero per 64-group). With K % 128 == 0
+    and N % 64 == 0, decode shapes (M <= 32) run the 4-bit weight-stream
+    kernels (w4_gemm.hip, ~3.5x less HBM traffic than bf16) and
+    32 < M <= _W4_TILED_MAX_M (large-batch decode, tree verify, chunked
+    prefill) the tiled kernel (w4_gemm_tiled.hip), which reads the same
+    codes and the bf16 activation as it is; no bf16 weight is materialised
+    on either. Anything else, and 32 < M with BBAMD_W4_TILED=0 (read per
+    call), dequantizes the whole weight and uses the library GEMM: above
+    the bound the GEMM is compute-bound and the library wins
+    (profiles/r10_w4_tiled.md)."""
     K = x.shape[-1]
     M = x.numel() // K
-    if (_on_gpu(x) and x.dtype == torch.bfloat16 and M <= 32
-            and K % 128 == 0 and N % 64 == 0):
+    gates = (_on_gpu(x) and x.dtype == torch.bfloat16 and K % 128 == 0
+             and N % 64 == 0)
+    if (gates and 32 < M <= _W4_TILED_MAX_M
+            and os.environ.get("BBAMD_W4_TILED", "1") != "0"):
+        _require_ext()
+        if residual is not None:
+            residual = residual.contiguous()
+        return hip_ops.gemm_w4(x.contiguous(), packed.reshape(N, K // 2),
+                               scale.reshape(N, K // 64).half(),
+                               zero.reshape(N, K // 64).half(),
+                               residual, bias, N, 0)
+    if gates and M <= 32:
         _require_ext()
         # the kernel computes in f16 (fast nibble->half dequant + f16 MFMA);
         # the activation conversion is M*K elements - noise next to the
