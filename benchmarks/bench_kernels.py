@@ -3,7 +3,7 @@
 Reports per-kernel time and effective HBM bandwidth / TFLOPs so kernel
 changes can be A/B'd without the end-to-end bench's noise.
 
-    python benchmarks/bench_kernels.py [attn_decode attn_mixed attn_prefill train_attn moe_w4 ...]
+    python benchmarks/bench_kernels.py [attn_decode attn_mixed attn_prefill attn_prefill_wide train_attn ...]
 """
 import math
 import os
@@ -182,6 +182,67 @@ def bench_attn_prefill():
         flops = B * Hq * D * 2 * 2 * (T * (T + 1) / 2)  # causal
         print(f"attn_prefill B{B} Hq{Hq}/{Hkv} T{T} D{D}: "
               f"{t*1e6:8.1f} us  {flops/t/1e12:7.1f} TF/s")
+
+
+def bench_attn_prefill_wide():
+    """Prefill at head dim 512 (attn_prefill_wide.hip) beside the torch
+    composition it replaces in ops.attn_prefill (ref.attn_paged on the device
+    tensors, what BBAMD_PREFILL_WIDE=0 runs), at the gemma4-9b global layer:
+    Hq=8, Hkv=4, scale 1.0. Three alternating rounds per case, each the median
+    of device-event timings that end in a synchronise; printed as median
+    [min..max]. TF/s counts the causal part only: 4 D FLOPs per (query, visible
+    key). `D256` is ops.attn_prefill at D=256 with Hq and Hkv doubled: the
+    same FLOPs and K/V bytes on attn_prefill_kernel<256>. Every page table
+    is 8192 positions wide, a session's capacity as the serving path passes
+    it, whatever the live context. After the three acceptance cases comes the
+    sweep behind the routing rule of ops.attn_prefill (few workgroups, short
+    to long live contexts); the last column is ops.attn_prefill itself, the
+    path that rule picks and its time with the rule's q_start read."""
+    from bloombee_amd.ops import interface as iface
+    Hq, Hkv, D, P = 8, 4, 512, 16
+    gen = torch.Generator(device=DEV).manual_seed(0)
+
+    def inputs(B, Tq, q_start, Hq, Hkv, D):
+        maxp = max(q_start + Tq, 8192) // P
+        rnd = lambda *sh: torch.randn(*sh, generator=gen, device=DEV,
+                                      dtype=torch.float32).to(torch.bfloat16)
+        kp, vp = rnd(B * maxp, Hkv, P, D), rnd(B * maxp, Hkv, D, P)
+        pt = torch.randperm(B * maxp, generator=gen, device=DEV).int().reshape(B, maxp)
+        q = rnd(B, Hq, Tq, D) * (2.0 / math.sqrt(D))
+        qs = torch.full((B,), q_start, dtype=torch.int32, device=DEV)
+        return q, kp, vp, pt, qs
+
+    cases = [(1, 2048, 0), (4, 512, 0), (1, 512, 7680)] + [
+        (1, 17, 500), (1, 64, 0), (1, 512, 0), (1, 64, 960), (1, 128, 896),
+        (1, 512, 512), (1, 64, 1984), (1, 128, 1920), (1, 512, 1536),
+        (1, 64, 4032), (1, 128, 3968), (1, 512, 3584), (1, 1024, 3072),
+        (1, 64, 8128), (1, 128, 8064), (1, 1024, 7168), (2, 512, 7680),
+        (4, 512, 7680), (1, 2048, 6144)]
+    for B, Tq, q_start in cases:
+        wide = inputs(B, Tq, q_start, Hq, Hkv, D)
+        half = inputs(B, Tq, q_start, 2 * Hq, 2 * Hkv, D // 2)
+        kernel = lambda: ops.hip_ops.attn_prefill(*wide, 1.0, 0, None, None)
+        comp = lambda: ref.attn_paged(*wide[:4], wide[4].long(), 1.0)
+        d256 = lambda: ops.attn_prefill(*half, scale=1.0)
+        routed = lambda: ops.attn_prefill(*wide, scale=1.0)
+        path = iface._prefill_kernel_ok(wide[0], wide[1], wide[3], wide[4])
+        err = (kernel().float() - comp().float()).abs().max().item()
+        tk, tc, th, tr = [], [], [], []
+        for _ in range(3):
+            tk.append(_event_time(kernel, 20, 5))
+            tc.append(_event_time(comp, 5, 2))
+            th.append(_event_time(d256, 20, 5))
+            tr.append(_event_time(routed, 10, 3))
+        tk.sort(), tc.sort(), th.sort(), tr.sort()
+        flops = 4.0 * D * B * Hq * (Tq * q_start + Tq * (Tq + 1) / 2)
+        us = lambda t: f"{t[1]*1e6:9.1f} us [{t[0]*1e6:.1f}..{t[2]*1e6:.1f}]"
+        print(f"attn_prefill_wide B{B} Tq{Tq} q_start{q_start}: "
+              f"kernel {us(tk)} {flops/tk[1]/1e12:6.1f} TF/s   "
+              f"composition {us(tc)} {flops/tc[1]/1e12:6.1f} TF/s   "
+              f"composition/kernel {tc[1]/tk[1]:6.1f} (worst case "
+              f"{tc[0]/tk[2]:.1f})   D256 {us(th)} {flops/th[1]/1e12:6.1f} TF/s   "
+              f"max|kernel - composition| {err:.4f}   ops.attn_prefill "
+              f"({'kernel' if path else 'composition'}) {us(tr)}", flush=True)
 
 
 def bench_kv_stream():
@@ -497,6 +558,7 @@ ALL = {
     "attn_mixed": bench_attn_mixed,
     "attn_sparse": bench_attn_sparse,
     "attn_prefill": bench_attn_prefill,
+    "attn_prefill_wide": bench_attn_prefill_wide,
     "train_attn": bench_train_attn,
     "kv_stream": bench_kv_stream,
     "norms": bench_norms,

@@ -6,6 +6,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <mutex>
 
 #include "common.h"
 
@@ -17,6 +18,7 @@
 #include "attn_decode_mfma.hip"
 #include "attn_sparse.hip"
 #include "attn_prefill.hip"
+#include "attn_prefill_wide.hip"
 #include "attn_train.hip"
 #include "gemm_skinny.hip"
 #include "moe_gemm.hip"
@@ -964,9 +966,30 @@ static torch::Tensor attn_prefill_core(
   auto* outp = ops.ptr<Bf16>(out, "out");
   TORCH_CHECK(kv.Hkv > 0, "empty KV pool");
   const int G = Hq / kv.Hkv;
-  dim3 grid((Tq + 127) / 128, B * Hq);
-  dispatch_head_dim<128, 64, 256, 32>(D, "attn_prefill", [&](auto d) {
-    attn_prefill_kernel<decltype(d)::value><<<grid, 512, 0, cur_stream()>>>(
+  dispatch_head_dim<128, 64, 256, 512, 32>(D, "attn_prefill", [&](auto d) {
+    constexpr int HD = decltype(d)::value;
+    // D=512 has a kernel of its own (attn_prefill_wide.hip): 64 q rows per
+    // workgroup and 100 KB of dynamic LDS, above the 64 KB a function gets
+    // by default, so its limit is raised once per device
+    constexpr bool WIDE = HD == PW_D;
+    constexpr int QROWS = WIDE ? PW_QROWS : 128;
+    constexpr int LDS = WIDE ? PW_LDS_BYTES : 0;
+    auto* kernel = [] {
+      if constexpr (WIDE) return &attn_prefill_wide_kernel;
+      else return &attn_prefill_kernel<HD>;
+    }();
+    if constexpr (WIDE) {
+      static std::once_flag raised[64];
+      const int dev = c10::hip::current_device();
+      TORCH_CHECK(dev >= 0 && dev < 64, "attn_prefill: device index ", dev);
+      std::call_once(raised[dev], [&] {
+        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   LDS));
+      });
+    }
+    dim3 grid((Tq + QROWS - 1) / QROWS, B * Hq);
+    kernel<<<grid, 512, LDS, cur_stream()>>>(
         qp, kv.k, kv.v, kv.pt, qsp, alibi_ptr, tm_ptr, outp, B, Hq, G, Tq, kv.P,
         kv.maxp, (int)window, (float)scale, q_sb, q_st, q_sh, out_sb, out_st,
         out_sh);

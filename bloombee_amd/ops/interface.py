@@ -163,6 +163,37 @@ def _sparse_kernel_ok(D: int, P: int) -> bool:
     return _SPARSE_KERNEL and D in (64, 128, 256) and P == 16
 
 
+# prefill at head dim 512 (Gemma-4 global layers): attn_prefill_wide.hip;
+# BBAMD_PREFILL_WIDE=0 falls back to the torch composition (ref.attn_paged
+# on the device tensors: one host sync per batch row, dense fp32 scores)
+_PREFILL_WIDE = os.environ.get("BBAMD_PREFILL_WIDE", "1") not in ("", "0")
+
+
+def _prefill_kernel_ok(q, k_pages, page_table, q_start) -> bool:
+    # head dims the prefill kernels cover: attn_prefill_kernel up to 256,
+    # attn_prefill_wide_kernel at 512; other wide dims run the composition.
+    # The wide kernel walks the whole context in each 64-row workgroup and
+    # does not split it, so a launch of few workgroups over a long context
+    # leaves most CUs idle: measured slower than the composition (0.4-0.9x,
+    # profiles/r11_prefill_wide.md) at <= 64 workgroups from 4k of live
+    # context and at <= 16 from 2k, so those stay on the composition.
+    D = q.shape[-1]
+    if D <= 256:
+        return True
+    if D != 512 or not _PREFILL_WIDE:
+        return False
+    B, Hq, Tq, _ = q.shape
+    workgroups = B * Hq * ((Tq + 63) // 64)
+    # page tables are as wide as the session's capacity, so the table only
+    # says where a long context is impossible; where it is possible, the
+    # longest live context costs one read of q_start (the composition this
+    # branch may pick syncs once per batch row)
+    if workgroups > 64 or page_table.shape[1] * k_pages.shape[2] < 2048:
+        return True
+    ctx = int(q_start.max()) + Tq
+    return not (ctx >= 4096 or (workgroups <= 16 and ctx >= 2048))
+
+
 def _alibi_on(alibi_slopes, dev):
     """The slopes as the kernels take them: contiguous f32 on dev, or None."""
     if alibi_slopes is None:
@@ -219,7 +250,7 @@ def attn_prefill(
         scale = 1.0 / math.sqrt(q.shape[-1])
     if _on_gpu(q):
         _require_ext()
-        if q.shape[-1] > 256:
+        if not _prefill_kernel_ok(q, k_pages, page_table, q_start):
             return ref.attn_paged(q, k_pages, v_pages, page_table,
                                   q_start.long(), scale,
                                   sliding_window=_window_or_none(window),
@@ -331,7 +362,8 @@ def attn_paged(q, k_pages, v_pages, page_table, q_start, scale=None, window: int
         if scale is None:
             scale = 1.0 / math.sqrt(q.shape[-1])
         if (_on_gpu(q) and _TREE_KERNEL and window == 0
-                and q.shape[-1] <= 256 and alibi_slopes is None):
+                and _prefill_kernel_ok(q, k_pages, page_table, q_start)
+                and alibi_slopes is None):
             # fused tree-mask prefill kernel (spec verify) — the default
             # GPU path (tests/test_treekernel.py parity on MI355X)
             _require_ext()
