@@ -49,6 +49,50 @@ def bench_attn_decode():
                   f"{t*1e6:8.1f} us  {bytes_/t/1e12:6.2f} TB/s")
 
 
+def bench_attn_decode_fp8():
+    """fp8 (e4m3) KV pool against the bf16 pool, llama-3-8b geometry: decode
+    attention at automatic n_split, the two alternating in one process, median
+    of 5 windows each; TB/s over the KV bytes each actually reads. Then prefill
+    of a 2k prompt the same way."""
+    Hq, Hkv, D, P = 32, 8, 128, 16
+    fp8 = torch.float8_e4m3fn
+
+    def med(fn, iters):
+        return sorted(timeit(fn, iters=iters, warmup=5) for _ in range(5))[2]
+
+    for ctx in (2048, 8192, 32768):
+        for B in (1, 8, 32):
+            maxp = ctx // P
+            kp = torch.randn(B * maxp, Hkv, P, D, dtype=torch.bfloat16, device=DEV)
+            vp = torch.randn(B * maxp, Hkv, D, P, dtype=torch.bfloat16, device=DEV)
+            kp8, vp8 = kp.to(fp8), vp.to(fp8)
+            pt = torch.arange(B * maxp, dtype=torch.int32, device=DEV).reshape(B, maxp)
+            q = torch.randn(B, Hq, 1, D, dtype=torch.bfloat16, device=DEV) * 0.1
+            ctx_l = torch.full((B,), ctx, dtype=torch.int32, device=DEV)
+            iters = max(20, min(400, (1 << 31) // (B * ctx * Hkv * D * 4)))
+            t16 = t8 = 0.0
+            for _ in range(2):      # alternate: bf16, fp8, bf16, fp8
+                t16 += med(lambda: ops.attn_decode(q, kp, vp, pt, ctx_l), iters) / 2
+                t8 += med(lambda: ops.attn_decode(q, kp8, vp8, pt, ctx_l), iters) / 2
+            b16 = B * Hkv * ctx * 2 * D * 2
+            print(f"attn_decode B{B} ctx{ctx}: bf16 {t16*1e6:8.1f} us "
+                  f"{b16/t16/1e12:5.2f} TB/s   fp8 {t8*1e6:8.1f} us "
+                  f"{b16/2/t8/1e12:5.2f} TB/s   bf16/fp8 {t16/t8:5.2f}", flush=True)
+            del kp, vp, kp8, vp8
+    B, T = 8, 2048
+    maxp = T // P
+    kp = torch.randn(B * maxp, Hkv, P, D, dtype=torch.bfloat16, device=DEV)
+    vp = torch.randn(B * maxp, Hkv, D, P, dtype=torch.bfloat16, device=DEV)
+    kp8, vp8 = kp.to(fp8), vp.to(fp8)
+    pt = torch.arange(B * maxp, dtype=torch.int32, device=DEV).reshape(B, maxp)
+    q = torch.randn(B, Hq, T, D, dtype=torch.bfloat16, device=DEV) * 0.1
+    qs = torch.zeros(B, dtype=torch.int32, device=DEV)
+    t16 = med(lambda: ops.attn_prefill(q, kp, vp, pt, qs), 20)
+    t8 = med(lambda: ops.attn_prefill(q, kp8, vp8, pt, qs), 20)
+    print(f"attn_prefill B{B} T{T}: bf16 {t16*1e6:8.1f} us   fp8 {t8*1e6:8.1f} us"
+          f"   bf16/fp8 {t16/t8:5.2f}", flush=True)
+
+
 def bench_attn_mixed():
     """Mixed-device decode, device side only: the decode kernel in
     forced-partial mode + the external-partial merge launch, against plain
@@ -555,6 +599,7 @@ def bench_w4_tiled():
 
 ALL = {
     "attn_decode": bench_attn_decode,
+    "attn_decode_fp8": bench_attn_decode_fp8,
     "attn_mixed": bench_attn_mixed,
     "attn_sparse": bench_attn_sparse,
     "attn_prefill": bench_attn_prefill,

@@ -42,6 +42,10 @@ def main():
                     help="cuda:0 / cpu (default: cuda if available)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--attn-cache-tokens", type=int, default=1 << 18)
+    ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
+                    help="resident KV page type (default: BBAMD_KV_DTYPE, "
+                         "bf16). fp8 = e4m3 pages, half the bytes per token: "
+                         "double --attn-cache-tokens for the same memory")
     ap.add_argument("--update-period", type=float, default=30.0)
     ap.add_argument("--checkpoint-dir", default=None,
                     help="per-block .npy weight dir (random init if absent)")
@@ -126,6 +130,7 @@ def main():
         announce_host=args.announce_host,
         announce_port=args.announce_port,
         quantize_q4=args.quant_type == "w4",
+        kv_dtype=args.kv_dtype,
     )
     server.run()
 

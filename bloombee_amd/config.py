@@ -25,6 +25,15 @@ def _parse_mixed(raw: str) -> str:
     return "off"
 
 
+def parse_kv_dtype(raw: str) -> str:
+    raw = raw.strip().lower()
+    if raw in ("fp8", "e4m3", "float8_e4m3fn"):
+        return "fp8"
+    if raw in ("bf16", "bfloat16", ""):
+        return "bf16"
+    raise ValueError(f"BBAMD_KV_DTYPE must be bf16 or fp8, got {raw!r}")
+
+
 def _env(name: str, default, cast=None):
     raw = os.environ.get(f"BBAMD_{name}")
     if raw is None:
@@ -43,6 +52,13 @@ class KVConfig:
     designed paged-first, SURVEY.md §7 hard-part 2)."""
 
     page_size: int = field(default_factory=lambda: _env("KV_PAGE_SIZE", 16))
+    # BBAMD_KV_DTYPE: element type of the resident KV pages. bf16 (default),
+    # or fp8: OCP e4m3, saturating, no scales — half the bytes per token, so
+    # twice the tokens per GB of pool (raise kv_max_tokens to use them) and
+    # half the bytes decode attention streams. Head dims 64 / 128 at page
+    # size 16 only; not with BBAMD_MIXED_ATTN (kv/paged.py kv_pool_dtype).
+    dtype: str = field(default_factory=lambda: parse_kv_dtype(
+        os.environ.get("BBAMD_KV_DTYPE", "bf16")))
     # Fraction of free device memory the KV pool may claim when the budget is
     # not set explicitly (the reference sizes from --attn_cache_tokens).
     max_tokens: Optional[int] = field(default_factory=lambda: _env("KV_MAX_TOKENS", None, int))

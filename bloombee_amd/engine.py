@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence
 import torch
 import torch.nn.functional as F
 
-from bloombee_amd.kv.paged import PagedKVCache, SessionHandle
+from bloombee_amd.kv.paged import PagedKVCache, SessionHandle, kv_pool_dtype
 from bloombee_amd.models.auto import get_block_class
 from bloombee_amd.models.base import ModelConfig, resolve_config
 from bloombee_amd.models.llama.block import RopeTables
@@ -54,7 +54,9 @@ class BlockStack(torch.nn.Module):
                                self.blocks[j - 1])
         self.device = torch.device(device)
 
-    def make_kv(self, max_tokens: int) -> PagedKVCache:
+    def make_kv(self, max_tokens: int,
+                kv_dtype: Optional[str] = None) -> PagedKVCache:
+        """kv_dtype: "bf16" / "fp8"; None takes BBAMD_KV_DTYPE."""
         # per-layer KV geometry hook (gemma-4 heterogeneous head_dim/kv heads)
         if hasattr(self.config, "kv_geometry"):
             hkv, dims = self.config.kv_geometry(self.start, self.end)
@@ -74,7 +76,7 @@ class BlockStack(torch.nn.Module):
             max_tokens=max_tokens,
             page_size=P,
             device=self.device,
-            dtype=self.config.dtype,
+            dtype=kv_pool_dtype(kv_dtype, self.config.dtype, dims, P),
         )
 
     @torch.no_grad()

@@ -51,6 +51,36 @@ class _SeqState:
     l_spec: int = 0   # committed + speculative tokens (>= l_acc)
 
 
+def kv_pool_dtype(kv_dtype: Optional[str], model_dtype: torch.dtype,
+                  head_dims, page_size: int, layout=None) -> torch.dtype:
+    """Element type of a new pool. kv_dtype: "bf16" / "fp8", or None for the
+    config's kv.dtype (BBAMD_KV_DTYPE). bf16 keeps the model's dtype. fp8
+    (torch.float8_e4m3fn) is refused here, at pool creation, for what the fp8
+    kernels do not cover, instead of at the first attention call."""
+    from bloombee_amd.config import get_config, parse_kv_dtype
+    cfg = get_config().kv
+    kind = parse_kv_dtype(kv_dtype) if kv_dtype is not None else cfg.dtype
+    if kind != "fp8":
+        return model_dtype
+    dims = sorted(set(head_dims if isinstance(head_dims, (list, tuple))
+                      else [head_dims]))
+    if any(d not in (64, 128) for d in dims):
+        raise ValueError(f"kv dtype fp8: head dims {dims} are not covered "
+                         "(the fp8 KV kernels take 64 and 128)")
+    if page_size != 16:
+        raise ValueError(f"kv dtype fp8 needs page size 16, got {page_size}")
+    if layout is not None and any(x != "kv" for x in layout):
+        raise ValueError("kv dtype fp8: k-only (k == v) layers are not covered")
+    if model_dtype != torch.bfloat16:
+        raise ValueError("kv dtype fp8 needs a bf16 model (the kernels read "
+                         f"bf16 q), got {model_dtype}")
+    if cfg.mixed_attn != "off":
+        raise ValueError("kv dtype fp8 cannot be combined with "
+                         "BBAMD_MIXED_ATTN: mixed-device decode has no fp8 "
+                         "kernel")
+    return torch.float8_e4m3fn
+
+
 class PagedKVCache:
     """Device-resident paged KV pool for a contiguous range of layers."""
 
@@ -415,7 +445,9 @@ class SessionHandle:
         debug_log("kv", get_logger(__name__),
                   "swap_out handle=%d to_disk=%s compress=%s",
                   self.handle_id, to_disk, compress)
-        if compress:
+        if compress and cache.dtype != torch.float8_e4m3fn:
+            # (an fp8 pool keeps the raw 1-byte snapshot: 4-bit requantising
+            # 8-bit data would stack a second, coarser rounding on the first)
             from bloombee_amd import ops as _ops
             comp = []
             for per_layer in snap:

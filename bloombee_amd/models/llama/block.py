@@ -263,7 +263,9 @@ class LlamaBlock(FamilyBlock):
         # the qkv GEMM's split-K combine folds into rope_kv_write: the GEMM
         # hands over its f32 slabs and the combine launch disappears
         # (a _post_qkv override needs combined values: no deferral then)
+        # (rope_kv_write_part has no fp8-pool variant: no deferral there)
         defer = (fuse_norm and type(self)._post_qkv is LlamaBlock._post_qkv
+                 and kv.k_pages(self.layer_index).dtype != torch.float8_e4m3fn
                  and ops.fuse_qkv_rope_ok(hidden, self.qkv_w, D))
         if fuse_norm and pb is not None and getattr(pb, "_ss_valid", False):
             # previous block's down-proj left sum-of-squares for `hidden`;

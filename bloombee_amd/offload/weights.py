@@ -211,8 +211,8 @@ class OffloadedBlockStack:
         return hidden
 
     # passthroughs
-    def make_kv(self, max_tokens: int):
-        return self.stack.make_kv(max_tokens)
+    def make_kv(self, max_tokens: int, kv_dtype=None):
+        return self.stack.make_kv(max_tokens, kv_dtype)
 
     @property
     def blocks(self):

@@ -24,11 +24,15 @@
 static constexpr int KVBLK = 32;
 
 
-template <int D>
+// KVT: the pool's element type. unsigned short = bf16 pages; unsigned char =
+// fp8 (e4m3) pages at page size 16, widened to bf16 (exactly) on the
+// global -> LDS staging step with 16 B loads of 16 elements; the LDS tiles and
+// everything after them are the same.
+template <int D, typename KVT = unsigned short>
 __global__ __launch_bounds__(512) void attn_prefill_kernel(
     const unsigned short* __restrict__ q,        // (B, Hq, Tq, D)
-    const unsigned short* __restrict__ k_pages,  // (np, Hkv, P, D)
-    const unsigned short* __restrict__ v_pages,
+    const KVT* __restrict__ k_pages,             // (np, Hkv, P, D)
+    const KVT* __restrict__ v_pages,
     const int* __restrict__ page_table,          // (B, maxp)
     const int* __restrict__ q_start,             // (B,)
     const float* __restrict__ alibi,             // (Hq,) slopes or null
@@ -96,6 +100,40 @@ __global__ __launch_bounds__(512) void attn_prefill_kernel(
 
   for (int kbase = kstart; kbase < kmax; kbase += KVBLK) {
     __syncthreads();  // everyone done reading previous tile
+    if constexpr (sizeof(KVT) == 1) {
+    // ---- fp8 pool: 16 elements per load, two 16 B LDS stores each. K: 16
+    // consecutive d of one key. V^T: one page row (16 positions at fixed d);
+    // kbase is KVBLK-aligned and P == 16, so a tile is two whole pages ----
+    for (int idx = tid; idx < KVBLK * (D / 16); idx += 512) {
+      const int t = idx / (D / 16);
+      const int d16 = (idx % (D / 16)) * 16;
+      const int kpos = kbase + t;
+      bf16x8 klo = as_bf16x8(short8{}), khi = klo;
+      if (kpos < ctx) {
+        const int page = page_table[b * maxp + kpos / P];
+        const long off =
+            (((long)page * (long)(Hq / G) + kvh) * P + (kpos % P)) * D + d16;
+        fp8x16_to_bf16(*reinterpret_cast<const int4v*>(k_pages + off), klo, khi);
+      }
+      unsigned char* dst = (unsigned char*)k_lds + t * KROW_B + d16 * 2;
+      *reinterpret_cast<bf16x8*>(dst) = klo;
+      *reinterpret_cast<bf16x8*>(dst + 16) = khi;
+    }
+    for (int idx = tid; idx < D * (KVBLK / 16); idx += 512) {
+      const int d = idx / (KVBLK / 16);
+      const int o16 = (idx % (KVBLK / 16)) * 16;
+      const int kpos = kbase + o16;
+      bf16x8 vlo = as_bf16x8(short8{}), vhi = vlo;
+      if (kpos < ctx) {
+        const int page = page_table[b * maxp + kpos / P];
+        fp8x16_to_bf16(*reinterpret_cast<const int4v*>(
+            v_pages + (((long)page * (long)(Hq / G) + kvh) * D + d) * P), vlo, vhi);
+      }
+      unsigned char* dst = (unsigned char*)v_lds + d * VROW_B + o16 * 2;
+      *reinterpret_cast<bf16x8*>(dst) = vlo;
+      *reinterpret_cast<bf16x8*>(dst + 16) = vhi;
+    }
+    } else {
     // ---- stage K tile (row-major, padded) ----
     for (int idx = tid; idx < KVBLK * (D / 8); idx += 512) {
       const int t = idx / (D / 8);
@@ -125,6 +163,7 @@ __global__ __launch_bounds__(512) void attn_prefill_kernel(
             (kpos % P));
       }
       *reinterpret_cast<short8*>((unsigned char*)v_lds + d * VROW_B + o8 * 2) = vv;
+    }
     }
     __syncthreads();
 

@@ -36,6 +36,53 @@ DEVINL unsigned short f2bf(float f) {
   return (unsigned short)(x >> 16);
 }
 
+// ---- fp8 (OCP e4m3) KV pages ----------------------------------------------
+// e4m3 -> bf16 is exact: 3 mantissa bits, and every e4m3 value down to the
+// subnormal 2^-9 is a NORMAL bf16, so the widened operands never touch the
+// MFMA's subnormal handling. v_cvt_pk_f32_fp8 gives two f32 whose low halves
+// are zero; their high halves are the bf16 bits, packed with one v_perm_b32.
+typedef __attribute__((ext_vector_type(4))) int int4v;  // 16 x e4m3 = 16 B
+typedef __attribute__((ext_vector_type(2))) int int2v;  //  8 x e4m3 =  8 B
+
+DEVINL unsigned int bf16_pair_of(f32x2 f) {
+  // bit-cast the whole vector, then index: __builtin_bit_cast of a vector
+  // ELEMENT reads element 0 whichever index is written (seen in the ISA)
+  typedef __attribute__((ext_vector_type(2))) unsigned int uint2v;
+  const uint2v u = __builtin_bit_cast(uint2v, f);
+  return __builtin_amdgcn_perm(u[1], u[0], 0x07060302u);
+}
+
+// 16 e4m3 bytes -> elements 0..7 and 8..15 as two bf16 MFMA fragments.
+DEVINL void fp8x16_to_bf16(int4v w, bf16x8& lo, bf16x8& hi) {
+  typedef __attribute__((ext_vector_type(4))) unsigned int uint4v;
+  uint4v a, b;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    a[2 * i] = bf16_pair_of(__builtin_amdgcn_cvt_pk_f32_fp8(w[i], false));
+    a[2 * i + 1] = bf16_pair_of(__builtin_amdgcn_cvt_pk_f32_fp8(w[i], true));
+    b[2 * i] = bf16_pair_of(__builtin_amdgcn_cvt_pk_f32_fp8(w[2 + i], false));
+    b[2 * i + 1] = bf16_pair_of(__builtin_amdgcn_cvt_pk_f32_fp8(w[2 + i], true));
+  }
+  lo = __builtin_bit_cast(bf16x8, a);
+  hi = __builtin_bit_cast(bf16x8, b);
+}
+
+// f32 -> e4m3 byte as the fp8 pool stores it: saturate to +-448 in f32 FIRST
+// (the convert's own overflow behaviour depends on mode bits), then round to
+// nearest even. NaN stays NaN.
+DEVINL float fp8_sat(float x) {
+  return (x != x) ? x : fminf(fmaxf(x, -448.f), 448.f);
+}
+DEVINL unsigned char f2fp8(float x) {
+  return (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(fp8_sat(x), 0.f, 0,
+                                                         false) & 0xff);
+}
+// four f32 -> four e4m3 bytes in one dword (element 0 in the low byte)
+DEVINL int f2fp8x4(float a, float b, float c, float d) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_sat(a), fp8_sat(b), 0, false);
+  return __builtin_amdgcn_cvt_pk_fp8_f32(fp8_sat(c), fp8_sat(d), w, true);
+}
+
 // Load 8 bf16 (16 B) and widen to f32.
 DEVINL void load_bf16x8(const unsigned short* p, float* out) {
   short8 v = *reinterpret_cast<const short8*>(p);

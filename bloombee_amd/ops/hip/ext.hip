@@ -28,6 +28,7 @@
 #include "mfma_selftest.hip"
 #include "quant4.hip"
 #include "wire.h"
+#include "kv_fp8.h"
 
 typedef __attribute__((ext_vector_type(8))) short short8_h;
 
@@ -52,6 +53,7 @@ using F32 = Elem<float, at::kFloat>;
 using I32 = Elem<int, at::kInt>;
 using U8 = Elem<unsigned char, at::kByte>;
 using Bool = Elem<unsigned char, at::kBool>;  // masks are read as bytes
+using F8 = Elem<unsigned char, at::kFloat8_e4m3fn>;  // fp8 KV pages, as bytes
 
 static const char* dtype_text(at::ScalarType st) {
   switch (st) {
@@ -60,6 +62,7 @@ static const char* dtype_text(at::ScalarType st) {
     case at::kFloat: return "f32";
     case at::kInt: return "int32";
     case at::kByte: return "u8";
+    case at::kFloat8_e4m3fn: return "fp8 (e4m3)";
     default: return "bool";
   }
 }
@@ -126,6 +129,47 @@ static PagedKV paged_kv(const Operands& ops, const torch::Tensor& k_pages,
   kv.Hkv = k_pages.size(1), kv.P = k_pages.size(2), kv.D = k_pages.size(3);
   kv.maxp = page_table.size(1);
   return kv;
+}
+
+// The same for an fp8 (e4m3) pool, with what the fp8 kernels (kv_fp8.hip)
+// assume of it: page size 16, head dim 64 or 128, V d-major, 16 B loads.
+static Fp8Pool paged_kv_fp8(const Operands& ops, const torch::Tensor& k_pages,
+                            const torch::Tensor& v_pages,
+                            const torch::Tensor& page_table) {
+  Fp8Pool kv;
+  kv.k = ops.ptr<F8>(k_pages, "k_pages");
+  kv.v = ops.ptr<F8>(v_pages, "v_pages");
+  kv.pt = ops.ptr<I32>(page_table, "page_table");
+  TORCH_CHECK(k_pages.dim() == 4 && v_pages.dim() == 4 && page_table.dim() == 2,
+              "bad KV pool / page table rank");
+  kv.Hkv = k_pages.size(1), kv.P = k_pages.size(2), kv.D = k_pages.size(3);
+  kv.maxp = page_table.size(1);
+  TORCH_CHECK(kv.P == 16, "fp8 KV pool: page size must be 16, got ", kv.P);
+  TORCH_CHECK(kv.D == 64 || kv.D == 128,
+              "fp8 KV pool: unsupported head_dim ", kv.D, " (supported: 64 128)");
+  TORCH_CHECK(v_pages.size(0) == k_pages.size(0) && v_pages.size(1) == kv.Hkv &&
+                  v_pages.size(2) == kv.D && v_pages.size(3) == kv.P,
+              "v_pages must be d-major (np, Hkv, D, P)");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(kv.k) | reinterpret_cast<uintptr_t>(kv.v)) % 16 == 0,
+              "fp8 KV pool must be 16 B aligned");
+  return kv;
+}
+
+// The ops that serve both pool types are templates on the pool struct
+// (pool_of<PagedKV> / pool_of<Fp8Pool>) behind one binding, which picks by the
+// pool's dtype: float8_e4m3fn pages are an fp8 pool, anything else goes to
+// paged_kv() and its bf16 check.
+static bool is_fp8_pool(const torch::Tensor& k_pages) {
+  return k_pages.scalar_type() == at::kFloat8_e4m3fn;
+}
+
+template <typename Pool>
+static Pool pool_of(const Operands& ops, const torch::Tensor& k_pages,
+                    const torch::Tensor& v_pages, const torch::Tensor& page_table) {
+  if constexpr (std::is_same_v<Pool, Fp8Pool>)
+    return paged_kv_fp8(ops, k_pages, v_pages, page_table);
+  else
+    return paged_kv(ops, k_pages, v_pages, page_table);
 }
 
 // What kv_write / kv_gather need beyond paged_kv(): they move 16 B (8 bf16)
@@ -597,9 +641,28 @@ torch::Tensor add_bf16(torch::Tensor a, torch::Tensor b) {
 // paged KV
 // ---------------------------------------------------------------------------
 
+static void kv_write_fp8(torch::Tensor k_new, torch::Tensor v_new, torch::Tensor k_pages,
+                  torch::Tensor v_pages, torch::Tensor page_table,
+                  torch::Tensor start_pos) {
+  Operands ops(k_new, "k_new");
+  const auto* knp = ops.ptr<Bf16>(k_new, "k_new");
+  const auto* vnp = ops.ptr<Bf16>(v_new, "v_new", true, k_new.numel());
+  const Fp8Pool kv = paged_kv_fp8(ops, k_pages, v_pages, page_table);
+  const auto* spp = ops.ptr<I32>(start_pos, "start_pos");
+  TORCH_CHECK(k_new.dim() == 4, "k_new must be (B, Hkv, T, D)");
+  const int B = k_new.size(0), T = k_new.size(2);
+  TORCH_CHECK(kv.Hkv == k_new.size(1) && kv.D == k_new.size(3));
+  TORCH_CHECK(start_pos.numel() >= B && page_table.size(0) >= B,
+              "kv_write: start_pos and page_table need a row per batch row");
+  if ((long)B * T == 0) return;
+  launch_kv_write_fp8(cur_stream(), knp, vnp, kv, spp, B, T);
+}
+
 void kv_write(torch::Tensor k_new, torch::Tensor v_new, torch::Tensor k_pages,
               torch::Tensor v_pages, torch::Tensor page_table,
               torch::Tensor start_pos) {
+  if (is_fp8_pool(k_pages))
+    return kv_write_fp8(k_new, v_new, k_pages, v_pages, page_table, start_pos);
   Operands ops(k_new, "k_new");
   const auto* knp = ops.ptr<Bf16>(k_new, "k_new");
   const auto* vnp = ops.ptr<Bf16>(v_new, "v_new", true, k_new.numel());
@@ -705,6 +768,7 @@ static auto attn_decode_kernel_for(DecodeVariant v) {
 
 // q is read in place through its batch / head strides (q_sb, q_sh), from
 // (B, Hq, 1, D) or from the q section of a fused QKV buffer; out likewise.
+template <typename Pool = PagedKV>
 static torch::Tensor attn_decode_core(
     const Operands& ops, const unsigned short* qp, const torch::Tensor& k_pages,
     const torch::Tensor& v_pages, const torch::Tensor& page_table,
@@ -713,7 +777,8 @@ static torch::Tensor attn_decode_core(
     int B, int Hq, int D, long q_sb, long q_sh,
     torch::Tensor out, long out_sb, long out_sh,
     const MixedExt* ext = nullptr) {
-  const PagedKV kv = paged_kv(ops, k_pages, v_pages, page_table);
+  constexpr bool FP8 = std::is_same_v<Pool, Fp8Pool>;
+  const Pool kv = pool_of<Pool>(ops, k_pages, v_pages, page_table);
   const int* ctxp = ops.ptr<I32>(ctx_lens, "ctx_lens");
   const float* alibi_ptr = ops.ptr<F32>(alibi, "alibi", true, Hq);
   auto* outp = ops.ptr<Bf16>(out, "out");
@@ -723,7 +788,9 @@ static torch::Tensor attn_decode_core(
   TORCH_CHECK(D != 256 || G <= 4, "D=256 decode supports GQA group size <= 4");
   const int nch = (G + 15) / 16;  // MQA chunks (falcon G=71 -> 5)
   const int maxg = (G <= 4 && nch == 1) ? 4 : 16;
-  const DecodeChoice choice = attn_decode_variant(D);
+  // attn_decode_fp8_kernel: 2 workgroups per CU (its launch bounds)
+  const DecodeChoice choice =
+      FP8 ? DecodeChoice{DecodeVariant::pipelined, 512} : attn_decode_variant(D);
   int n_split = (int)n_split_req;
   if (n_split <= 0)
     n_split = (int)std::max<long>(
@@ -742,6 +809,20 @@ static torch::Tensor attn_decode_core(
   }
   float* pmlp = ops.ptr<F32>(pml, "pml");
   float* paccp = ops.ptr<F32>(pacc, "pacc");
+  if constexpr (FP8) {
+    TORCH_CHECK(ext == nullptr, "fp8 KV pool: no mixed-device decode");
+    TORCH_CHECK(D == kv.D, "q head_dim ", D, " != pool head_dim ", kv.D);
+    launch_attn_decode_fp8(cur_stream(), qp, kv, ctxp, alibi_ptr, outp, pmlp,
+                           paccp, B, G, nch, maxg, n_split, (int)window,
+                           (float)scale, q_sb, q_sh, out_sb, out_sh);
+    if (n_split > 1)
+      dispatch_head_dim<128, 64>(D, "attn_decode (fp8 KV)", [&](auto d) {
+        attn_decode_combine_kernel<decltype(d)::value>
+            <<<B * Hkv * nch, maxg * 16, 0, cur_stream()>>>(
+                pmlp, paccp, outp, Hkv, G, nch, maxg, n_split, out_sb, out_sh);
+      });
+    return out;
+  } else {
   const dim3 grid(B * Hkv * nch, n_split);
   dispatch_head_dim<128, 64, 256, 512, 32>(D, "attn_decode", [&](auto d) {
     constexpr int DD = decltype(d)::value;
@@ -763,9 +844,11 @@ static torch::Tensor attn_decode_core(
     }
   });
   return out;
+  }
 }
 
-torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k_pages,
+template <typename Pool>
+static torch::Tensor attn_decode_t(torch::Tensor q, torch::Tensor k_pages,
                           torch::Tensor v_pages, torch::Tensor page_table,
                           torch::Tensor ctx_lens, double scale, long window,
                           long n_split_req,
@@ -775,30 +858,51 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k_pages,
   TORCH_CHECK(q.dim() == 4 && q.size(2) == 1, "attn_decode expects (B, Hq, 1, D)");
   const int B = q.size(0), Hq = q.size(1), D = q.size(3);
   auto out = torch::empty({B, Hq, 1, D}, q.options());
-  return attn_decode_core(ops, qp, k_pages, v_pages, page_table, ctx_lens, alibi,
-                          scale, window, n_split_req, B, Hq, D,
-                          (long)Hq * D, (long)D, out, (long)Hq * D, (long)D);
+  return attn_decode_core<Pool>(ops, qp, k_pages, v_pages, page_table, ctx_lens,
+                                alibi, scale, window, n_split_req, B, Hq, D,
+                                (long)Hq * D, (long)D, out, (long)Hq * D, (long)D);
 }
 
 // Fused-QKV decode: q section of qkv (B, 1, (Hq+2Hkv)*D) read in place,
 // out (B, 1, Hq*D) ready for the O-projection GEMM — zero transposes.
-torch::Tensor attn_decode_qkv(torch::Tensor qkv, long Hq, torch::Tensor k_pages,
+torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k_pages,
+                          torch::Tensor v_pages, torch::Tensor page_table,
+                          torch::Tensor ctx_lens, double scale, long window,
+                          long n_split_req,
+                          c10::optional<torch::Tensor> alibi) {
+  auto f = is_fp8_pool(k_pages) ? &attn_decode_t<Fp8Pool> : &attn_decode_t<PagedKV>;
+  return f(q, k_pages, v_pages, page_table, ctx_lens, scale, window,
+           n_split_req, alibi);
+}
+
+template <typename Pool>
+static torch::Tensor attn_decode_qkv_t(torch::Tensor qkv, long Hq, torch::Tensor k_pages,
                               torch::Tensor v_pages, torch::Tensor page_table,
                               torch::Tensor ctx_lens, double scale, long window,
                               long n_split_req) {
   Operands ops(qkv, "qkv");
   const auto* qp = ops.ptr<Bf16>(qkv, "qkv");
-  const PagedKV kv = paged_kv(ops, k_pages, v_pages, page_table);
+  const Pool kv = pool_of<Pool>(ops, k_pages, v_pages, page_table);
   const int Hkv = kv.Hkv, D = kv.D;
   const int B = qkv.size(0);
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(1) == 1 &&
               qkv.size(2) == (Hq + 2 * Hkv) * D, "bad fused qkv shape");
   auto out = torch::empty({B, 1, Hq * D}, qkv.options());
-  return attn_decode_core(ops, qp, k_pages, v_pages, page_table, ctx_lens,
+  return attn_decode_core<Pool>(ops, qp, k_pages, v_pages, page_table, ctx_lens,
                           c10::nullopt, scale, window, n_split_req, B, (int)Hq,
                           D, (long)(Hq + 2 * Hkv) * D, (long)D,
                           out, (long)Hq * D, (long)D)
       .view({B, 1, Hq * D});
+}
+
+torch::Tensor attn_decode_qkv(torch::Tensor qkv, long Hq, torch::Tensor k_pages,
+                              torch::Tensor v_pages, torch::Tensor page_table,
+                              torch::Tensor ctx_lens, double scale, long window,
+                              long n_split_req) {
+  auto f = is_fp8_pool(k_pages) ? &attn_decode_qkv_t<Fp8Pool>
+                                : &attn_decode_qkv_t<PagedKV>;
+  return f(qkv, Hq, k_pages, v_pages, page_table, ctx_lens, scale, window,
+           n_split_req);
 }
 
 // ---------------------------------------------------------------------------
@@ -947,6 +1051,7 @@ torch::Tensor attn_decode_mixed(torch::Tensor q, torch::Tensor k_pages,
 
 // q and out are read / written in place through their (batch, token, head)
 // strides: (B, Hq, Tq, D) tensors or the fused (B, Tq, heads * D) layouts.
+template <typename Pool>
 static torch::Tensor attn_prefill_core(
     const Operands& ops, const unsigned short* qp, const torch::Tensor& k_pages,
     const torch::Tensor& v_pages, const torch::Tensor& page_table,
@@ -954,7 +1059,7 @@ static torch::Tensor attn_prefill_core(
     const c10::optional<torch::Tensor>& tree_mask, double scale, long window,
     int B, int Hq, int Tq, int D, long q_sb, long q_st, long q_sh,
     torch::Tensor out, long out_sb, long out_st, long out_sh) {
-  const PagedKV kv = paged_kv(ops, k_pages, v_pages, page_table);
+  const Pool kv = pool_of<Pool>(ops, k_pages, v_pages, page_table);
   const int* qsp = ops.ptr<I32>(q_start, "q_start");
   const float* alibi_ptr = ops.ptr<F32>(alibi, "alibi", true, Hq);
   const unsigned char* tm_ptr = ops.ptr<Bool>(tree_mask, "tree_mask");
@@ -965,6 +1070,14 @@ static torch::Tensor attn_prefill_core(
   }
   auto* outp = ops.ptr<Bf16>(out, "out");
   TORCH_CHECK(kv.Hkv > 0, "empty KV pool");
+  if constexpr (std::is_same_v<Pool, Fp8Pool>) {
+    TORCH_CHECK(D == kv.D, "q head_dim ", D, " != pool head_dim ", kv.D);
+    TORCH_CHECK(Hq % kv.Hkv == 0, "Hq must be a multiple of Hkv");
+    launch_attn_prefill_fp8(cur_stream(), qp, kv, qsp, alibi_ptr, tm_ptr, outp,
+                            B, Hq, Tq, (int)window, (float)scale, q_sb, q_st,
+                            q_sh, out_sb, out_st, out_sh);
+    return out;
+  } else {
   const int G = Hq / kv.Hkv;
   dispatch_head_dim<128, 64, 256, 512, 32>(D, "attn_prefill", [&](auto d) {
     constexpr int HD = decltype(d)::value;
@@ -995,9 +1108,11 @@ static torch::Tensor attn_prefill_core(
         out_sh);
   });
   return out;
+  }
 }
 
-torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor k_pages,
+template <typename Pool>
+static torch::Tensor attn_prefill_t(torch::Tensor q, torch::Tensor k_pages,
                            torch::Tensor v_pages, torch::Tensor page_table,
                            torch::Tensor q_start, double scale, long window,
                            c10::optional<torch::Tensor> alibi,
@@ -1006,7 +1121,7 @@ torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor k_pages,
   const auto* qp = ops.ptr<Bf16>(q, "q");
   TORCH_CHECK(q.dim() == 4, "attn_prefill expects (B, Hq, Tq, D)");
   const int B = q.size(0), Hq = q.size(1), Tq = q.size(2), D = q.size(3);
-  return attn_prefill_core(
+  return attn_prefill_core<Pool>(
       ops, qp, k_pages, v_pages, page_table, q_start, alibi, tree_mask, scale,
       window, B, Hq, Tq, D, (long)Hq * Tq * D, (long)D, (long)Tq * D,
       torch::empty_like(q), (long)Hq * Tq * D, (long)D, (long)Tq * D);
@@ -1014,18 +1129,29 @@ torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor k_pages,
 
 // Fused-QKV prefill: q read from qkv (B, Tq, (Hq+2Hkv)*D) in place,
 // out (B, Tq, Hq*D) ready for the O-projection GEMM.
-torch::Tensor attn_prefill_qkv(torch::Tensor qkv, long Hq_,
+torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor k_pages,
+                           torch::Tensor v_pages, torch::Tensor page_table,
+                           torch::Tensor q_start, double scale, long window,
+                           c10::optional<torch::Tensor> alibi,
+                           c10::optional<torch::Tensor> tree_mask) {
+  auto f = is_fp8_pool(k_pages) ? &attn_prefill_t<Fp8Pool> : &attn_prefill_t<PagedKV>;
+  return f(q, k_pages, v_pages, page_table, q_start, scale, window, alibi,
+           tree_mask);
+}
+
+template <typename Pool>
+static torch::Tensor attn_prefill_qkv_t(torch::Tensor qkv, long Hq_,
                                torch::Tensor k_pages, torch::Tensor v_pages,
                                torch::Tensor page_table, torch::Tensor q_start,
                                double scale, long window) {
   Operands ops(qkv, "qkv");
   const auto* qp = ops.ptr<Bf16>(qkv, "qkv");
-  const PagedKV kv = paged_kv(ops, k_pages, v_pages, page_table);
+  const Pool kv = pool_of<Pool>(ops, k_pages, v_pages, page_table);
   const int Hq = (int)Hq_, D = kv.D;
   const int X = Hq + 2 * kv.Hkv;
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == (long)X * D, "bad fused qkv shape");
   const int B = qkv.size(0), Tq = qkv.size(1);
-  return attn_prefill_core(
+  return attn_prefill_core<Pool>(
       ops, qp, k_pages, v_pages, page_table, q_start, c10::nullopt, c10::nullopt,
       scale, window, B, Hq, Tq, D, (long)Tq * X * D, (long)X * D, (long)D,
       torch::empty({B, Tq, (long)Hq * D}, qkv.options()), (long)Tq * Hq * D,
@@ -1037,6 +1163,15 @@ torch::Tensor attn_prefill_qkv(torch::Tensor qkv, long Hq_,
 // ---------------------------------------------------------------------------
 
 // (B, T, H, D) bf16 view with a contiguous last dim and 16-byte aligned rows.
+torch::Tensor attn_prefill_qkv(torch::Tensor qkv, long Hq,
+                               torch::Tensor k_pages, torch::Tensor v_pages,
+                               torch::Tensor page_table, torch::Tensor q_start,
+                               double scale, long window) {
+  auto f = is_fp8_pool(k_pages) ? &attn_prefill_qkv_t<Fp8Pool>
+                                : &attn_prefill_qkv_t<PagedKV>;
+  return f(qkv, Hq, k_pages, v_pages, page_table, q_start, scale, window);
+}
+
 static unsigned short* train_operand(const Operands& ops, const torch::Tensor& t,
                                      const char* name, long B, long T, long D) {
   auto* p = ops.ptr<Bf16>(t, name, STRIDED);
@@ -1173,10 +1308,35 @@ static void rope_kv_write_launch(
   }
 }
 
+// rope_kv_write_ into an fp8 pool: the q section as above to the bit, K roped
+// in f32 and rounded once to e4m3, V clamped and converted.
+static void rope_kv_write_fp8_(torch::Tensor qkv, long Hq_, long Hkv_, torch::Tensor cos_t,
+                        torch::Tensor sin_t, c10::optional<torch::Tensor> pos,
+                        torch::Tensor k_pages, torch::Tensor v_pages,
+                        torch::Tensor page_table, torch::Tensor start_pos) {
+  Operands ops(qkv, "qkv");
+  const Fp8Pool kv = paged_kv_fp8(ops, k_pages, v_pages, page_table);
+  const int Hq = (int)Hq_, B = qkv.size(0), T = qkv.size(1);
+  TORCH_CHECK(Hkv_ == kv.Hkv && qkv.dim() == 3 &&
+              qkv.size(2) == (long)(Hq + 2 * kv.Hkv) * kv.D, "bad fused qkv shape");
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == kv.D / 2 &&
+              sin_t.sizes() == cos_t.sizes(), "rope tables must be (max_pos, D/2)");
+  TORCH_CHECK(start_pos.numel() >= B && page_table.size(0) >= B,
+              "rope_kv_write_: start_pos and page_table need a row per batch row");
+  if ((long)B * T == 0) return;
+  launch_rope_kv_write_fp8(
+      cur_stream(), ops.ptr<Bf16>(qkv, "qkv"), ops.ptr<F32>(cos_t, "cos_t"),
+      ops.ptr<F32>(sin_t, "sin_t"), ops.ptr<I32>(pos, "pos", true, (long)B * T),
+      kv, ops.ptr<I32>(start_pos, "start_pos"), B, Hq, T, (int)cos_t.size(0));
+}
+
 void rope_kv_write_(torch::Tensor qkv, long Hq_, long Hkv_, torch::Tensor cos_t,
                     torch::Tensor sin_t, c10::optional<torch::Tensor> pos,
                     torch::Tensor k_pages, torch::Tensor v_pages,
                     torch::Tensor page_table, torch::Tensor start_pos) {
+  if (is_fp8_pool(k_pages))
+    return rope_kv_write_fp8_(qkv, Hq_, Hkv_, cos_t, sin_t, pos, k_pages,
+                              v_pages, page_table, start_pos);
   Operands ops(qkv, "qkv");
   const PagedKV kv = paged_kv(ops, k_pages, v_pages, page_table);
   const int Hq = (int)Hq_, Hkv = (int)Hkv_;

@@ -100,9 +100,40 @@ def gelu_tanh(x: torch.Tensor) -> torch.Tensor:
     return ref.gelu_tanh(x)
 
 
+FP8_KV = torch.float8_e4m3fn
+
+
+def _fp8_pool(k_pages: torch.Tensor) -> bool:
+    """An fp8 (e4m3) KV pool: pages hold e4m3_rne(clamp(x, -448, 448)) of the
+    bf16 value a bf16 pool would hold, no scales; attention over it is the
+    bf16 path's attention over the dequantised pages. On the GPU every op
+    that takes pages has an fp8 kernel of its own (kv_fp8.hip) for head dims
+    64 / 128 at page size 16; what has none raises (_fp8_refuse)."""
+    return k_pages.dtype == FP8_KV
+
+
+def _fp8_refuse(what: str):
+    raise RuntimeError(f"fp8 KV pool + {what}: no kernel for this combination "
+                       "(use BBAMD_KV_DTYPE=bf16)")
+
+
+def _fp8_check(k_pages):
+    """Device fp8 pool: the geometry the fp8 kernels cover, by name."""
+    D, P = k_pages.shape[3], k_pages.shape[2]
+    if D not in (64, 128):
+        _fp8_refuse(f"head_dim {D} (kernels cover 64 and 128)")
+    if P != 16:
+        _fp8_refuse(f"page size {P} (kernels cover 16)")
+
+
 def kv_write(k_new, v_new, k_pages, v_pages, page_table, start_pos):
     if _on_gpu(k_new):
         _require_ext()
+        if _fp8_pool(k_pages):
+            _fp8_check(k_pages)
+            hip_ops.kv_write(k_new.contiguous(), v_new.contiguous(),
+                                 k_pages, v_pages, page_table, start_pos.int())
+            return
         hip_ops.kv_write(k_new.contiguous(), v_new.contiguous(), k_pages, v_pages,
                          page_table, start_pos.int())
         return
@@ -212,6 +243,15 @@ def attn_decode(
     """Single-token paged attention. q: (B, Hq, 1, D)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if _on_gpu(q) and _fp8_pool(k_pages):
+        _require_ext()
+        if _attn_sparsity < 1.0 and window <= 0:
+            _fp8_refuse("sparse decode (attn_sparsity < 1)")
+        _fp8_check(k_pages)
+        al = _alibi_on(alibi_slopes, q.device)
+        return hip_ops.attn_decode(q.contiguous(), k_pages, v_pages,
+                                       page_table, ctx_lens.int(), scale,
+                                       window, n_split, al)
     if _attn_sparsity < 1.0 and window <= 0:
         if _on_gpu(q) and _sparse_kernel_ok(q.shape[-1], k_pages.shape[2]):
             _require_ext()
@@ -250,6 +290,12 @@ def attn_prefill(
         scale = 1.0 / math.sqrt(q.shape[-1])
     if _on_gpu(q):
         _require_ext()
+        if _fp8_pool(k_pages):
+            _fp8_check(k_pages)
+            al = _alibi_on(alibi_slopes, q.device)
+            return hip_ops.attn_prefill(q.contiguous(), k_pages, v_pages,
+                                            page_table, q_start.int(), scale,
+                                            window, al, None)
         if not _prefill_kernel_ok(q, k_pages, page_table, q_start):
             return ref.attn_paged(q, k_pages, v_pages, page_table,
                                   q_start.long(), scale,
@@ -272,6 +318,13 @@ def rope_kv_write_(qkv, Hq: int, Hkv: int, cos, sin, position_ids,
     """
     if _on_gpu(qkv):
         _require_ext()
+        if _fp8_pool(k_pages):
+            _fp8_check(k_pages)
+            hip_ops.rope_kv_write_(
+                qkv, Hq, Hkv, cos, sin,
+                position_ids.int() if position_ids is not None else None,
+                k_pages, v_pages, page_table, start_pos.int())
+            return
         hip_ops.rope_kv_write_(qkv, Hq, Hkv, cos, sin,
                                position_ids.int() if position_ids is not None else None,
                                k_pages, v_pages, page_table, start_pos.int())
@@ -285,6 +338,9 @@ def rope_kv_write_(qkv, Hq: int, Hkv: int, cos, sin, position_ids,
         position_ids = start_pos.view(B, 1).long() + torch.arange(T).view(1, T)
     q2, k2 = ref.rope_apply(q, k, cos, sin, position_ids)
     qkv[..., : Hq * D].copy_(q2.permute(0, 2, 1, 3).reshape(B, T, Hq * D))
+    if _fp8_pool(k_pages):
+        # K is roped in f32 and rounded once to e4m3, not via bf16
+        k2 = ref.rope_apply(q.float(), k.float(), cos, sin, position_ids)[1]
     ref.kv_write(k2, v.contiguous(), k_pages, v_pages, page_table, start_pos)
 
 
@@ -300,6 +356,8 @@ def rope_kv_write_part(part, bias, B: int, T: int, Hq: int, Hkv: int, cos, sin,
     the (B,) int32 context lengths start_pos + T, which attn_paged_qkv takes
     as ctx_lens at T == 1 instead of launching its own start_pos + 1."""
     _require_ext()
+    if _fp8_pool(k_pages):
+        _fp8_refuse("the deferred split-K rope_kv_write_part")
     return hip_ops.rope_kv_write_part(
         part, bias, B, T, Hq, Hkv, cos, sin,
         position_ids.int() if position_ids is not None else None,
@@ -320,6 +378,19 @@ def attn_paged_qkv(qkv, Hq: int, Hkv: int, k_pages, v_pages, page_table,
     D = k_pages.shape[3]
     if scale is None:
         scale = 1.0 / math.sqrt(D)
+    if _on_gpu(qkv) and _fp8_pool(k_pages):
+        _require_ext()
+        if _attn_sparsity < 1.0 and T == 1 and window <= 0:
+            _fp8_refuse("sparse decode (attn_sparsity < 1)")
+        _fp8_check(k_pages)
+        if T == 1:
+            ctx = ctx_lens if ctx_lens is not None else q_start + 1
+            return hip_ops.attn_decode_qkv(qkv, Hq, k_pages, v_pages,
+                                               page_table, ctx.int(), scale,
+                                               window, 0)
+        return hip_ops.attn_prefill_qkv(qkv, Hq, k_pages, v_pages,
+                                            page_table, q_start.int(), scale,
+                                            window)
     if _attn_sparsity < 1.0 and T == 1 and window <= 0:
         ctx = ctx_lens if ctx_lens is not None else q_start + 1
         if (_on_gpu(qkv) and _sparse_kernel_ok(D, k_pages.shape[2])
@@ -361,6 +432,15 @@ def attn_paged(q, k_pages, v_pages, page_table, q_start, scale=None, window: int
     if tree_mask is not None:
         if scale is None:
             scale = 1.0 / math.sqrt(q.shape[-1])
+        if _on_gpu(q) and _fp8_pool(k_pages):
+            _require_ext()
+            _fp8_check(k_pages)
+            if window != 0 or alibi_slopes is not None:
+                _fp8_refuse("tree_mask with a sliding window or ALiBi")
+            tm = tree_mask.to(q.device).contiguous().bool()
+            return hip_ops.attn_prefill(q.contiguous(), k_pages, v_pages,
+                                            page_table, q_start.int(), scale,
+                                            0, None, tm)
         if (_on_gpu(q) and _TREE_KERNEL and window == 0
                 and _prefill_kernel_ok(q, k_pages, page_table, q_start)
                 and alibi_slopes is None):
@@ -625,6 +705,8 @@ def attn_paged_mixed(q, k_pages, v_pages, page_table, ctx_lens,
     D = q.shape[-1]
     if scale is None:
         scale = 1.0 / math.sqrt(D)
+    if _on_gpu(q) and _fp8_pool(k_pages):
+        _fp8_refuse("a host prefix (mixed-device decode)")
     if _on_gpu(q) and _mixed_kernel_ok(D):
         B, Hq = q.shape[0], q.shape[1]
         out = _attn_mixed_gpu(q.contiguous(), q, k_pages, v_pages, page_table,
@@ -647,6 +729,8 @@ def attn_paged_mixed_qkv(qkv, Hq: int, Hkv: int, k_pages, v_pages, page_table,
     D = k_pages.shape[3]
     if scale is None:
         scale = 1.0 / math.sqrt(D)
+    if _on_gpu(qkv) and _fp8_pool(k_pages):
+        _fp8_refuse("a host prefix (mixed-device decode)")
     q = qkv[..., : Hq * D].view(B, T, Hq, D).permute(0, 2, 1, 3)
     if _on_gpu(qkv) and _mixed_kernel_ok(D) and qkv.is_contiguous():
         return _attn_mixed_gpu(qkv, q, k_pages, v_pages, page_table, ctx_lens,

@@ -166,6 +166,10 @@ def kv_write(
     """
     B, Hkv, T, D = k_new.shape
     P = k_pages.shape[2]
+    if k_pages.dtype == torch.float8_e4m3fn:
+        # fp8 pool: saturate (torch's own cast turns |x| > 448 into NaN)
+        k_new = k_new.float().clamp(-448, 448).to(k_pages.dtype)
+        v_new = v_new.float().clamp(-448, 448).to(v_pages.dtype)
     for b in range(B):
         s = int(start_pos[b])
         for t in range(T):

@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 from bloombee_amd import ops
 from bloombee_amd.engine import BlockStack
-from bloombee_amd.kv.paged import PagedKVCache, SessionHandle
+from bloombee_amd.kv.paged import PagedKVCache, SessionHandle, kv_pool_dtype
 from bloombee_amd.models.base import ModelConfig
 from bloombee_amd.models.llama.block import LlamaBlock
 from bloombee_amd.utils.logging import get_logger
@@ -129,14 +129,16 @@ class TPBlockStack:
             for b in full.blocks])
         del full
 
-    def make_kv(self, max_tokens: int) -> PagedKVCache:
+    def make_kv(self, max_tokens: int,
+                kv_dtype: Optional[str] = None) -> PagedKVCache:
         return PagedKVCache(
             num_layers=len(self.blocks),
             num_kv_heads=self.config.num_key_value_heads // self.tp_world,
             head_dim=self.config.head_dim,
             max_tokens=max_tokens,
             device=self.device,
-            dtype=self.config.dtype,
+            dtype=kv_pool_dtype(kv_dtype, self.config.dtype,
+                                self.config.head_dim, 16),
         )
 
     @torch.no_grad()

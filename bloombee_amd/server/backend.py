@@ -40,7 +40,8 @@ class StackBackend:
                  checkpoint_dir: Optional[str] = None,
                  offload_policy=None,
                  max_batch_size: int = 2048,
-                 quantize_q4: bool = False):
+                 quantize_q4: bool = False,
+                 kv_dtype: Optional[str] = None):
         self.config = config
         self.start, self.end = start, end
         self.device = torch.device(device)
@@ -73,7 +74,8 @@ class StackBackend:
             _ops.set_attn_sparsity(offload_policy.attn_sparsity)
         self.compress_swap = bool(offload_policy is not None
                                   and offload_policy.compress_cache)
-        self.kv_pool: PagedKVCache = self.stack.make_kv(kv_max_tokens)
+        # kv_dtype: "bf16" / "fp8" resident pages; None = BBAMD_KV_DTYPE
+        self.kv_pool: PagedKVCache = self.stack.make_kv(kv_max_tokens, kv_dtype)
         self.is_last_block = (end == config.num_hidden_layers)
         self.pruner = None
         if self.is_last_block:

@@ -56,6 +56,7 @@ class Server:
         announce_host: Optional[str] = None,
         announce_port: Optional[int] = None,
         quantize_q4: bool = False,
+        kv_dtype: Optional[str] = None,
     ):
         self.config = model if isinstance(model, ModelConfig) else resolve_config(model)
         self.model_name = model_name or (model if isinstance(model, str)
@@ -115,7 +116,8 @@ class Server:
                                 checkpoint_dir=checkpoint_dir,
                                 offload_policy=offload_policy,
                                 max_batch_size=max_batch_size,
-                                quantize_q4=quantize_q4)
+                                quantize_q4=quantize_q4,
+                                kv_dtype=kv_dtype)
         self.backend = StackBackend(self.config, block_indices[0],
                                     block_indices[1], **self._backend_kw)
         if adapters:

@@ -32,10 +32,21 @@ def build(verbose: bool = True) -> Path:
     py_inc = sysconfig.get_paths()["include"]
     src = HIP_DIR / "ext.hip"
     obj = HIP_DIR / "ext.o"
-    compile_cmd = [
+    # the fp8 KV kernels are a translation unit of their own (raw-pointer
+    # launchers, no torch headers), built without packed-fp32 instructions
+    kv8_src = HIP_DIR / "kv_fp8.hip"
+    kv8_obj = HIP_DIR / "kv_fp8.o"
+    hipcc = [
         "/opt/rocm/bin/hipcc",
         f"--offload-arch={ARCH}",
         "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
+    ]
+    kv8_cmd = hipcc + [
+        "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
+        "-I", "/opt/rocm/include", "-D__HIP_PLATFORM_AMD__=1",
+        "-c", str(kv8_src), "-o", str(kv8_obj),
+    ]
+    compile_cmd = hipcc + [
         "-I", str(tinc),
         "-I", str(tinc / "torch" / "csrc" / "api" / "include"),
         "-I", "/opt/rocm/include",
@@ -47,17 +58,18 @@ def build(verbose: bool = True) -> Path:
         "-c", str(src), "-o", str(obj),
     ]
     link_cmd = [
-        "g++", "-shared", str(obj),
+        "g++", "-shared", str(obj), str(kv8_obj),
         "-L", str(tlib), "-L", "/opt/rocm/lib",
         "-lc10", "-ltorch", "-ltorch_cpu", "-ltorch_python",
         "-lamdhip64", "-lc10_hip", "-ltorch_hip", "-lz",
         "-o", str(OUT_SO),
     ]
-    for cmd in (compile_cmd, link_cmd):
+    for cmd in (compile_cmd, kv8_cmd, link_cmd):
         if verbose:
             print("+", " ".join(cmd), file=sys.stderr)
         subprocess.run(cmd, check=True)
     obj.unlink(missing_ok=True)
+    kv8_obj.unlink(missing_ok=True)
     return OUT_SO
 
 
