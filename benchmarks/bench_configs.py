@@ -335,7 +335,30 @@ def bench_families(steps=24):
             print(json.dumps({"family_bench": name, "error": str(e)[:200]}))
 
 
+def bench_weight_tiers(steps=48, B=32, prompt=2048):
+    """Flagship decode (llama-3-8b, batch 32, 2k prompt) through LocalEngine
+    per weight tier: the default bf16 path, quantize_fp8 (gemm_w8.hip) and
+    quantize_q4, one engine at a time in one process, two rounds each."""
+    from bloombee_amd.engine import LocalEngine
+
+    tiers = (("bf16", {}), ("fp8", {"quantize_fp8": True}),
+             ("w4", {"quantize_q4": True}))
+    for rnd in range(2):
+        for tag, kw in tiers:
+            eng = LocalEngine("llama-3-8b" if DEV != "cpu" else "llama-tiny",
+                              device=DEV, seed=0,
+                              kv_max_tokens=B * (prompt + steps + 32) + 1024, **kw)
+            tps, ms = _decode_loop(eng, B, prompt, steps)
+            print(json.dumps({"weight_tier": tag, "round": rnd, "batch": B,
+                              "prompt": prompt, "tokens_per_s": round(tps, 1),
+                              "ms_per_step": round(ms, 2)}), flush=True)
+            del eng
+            if DEV.startswith("cuda"):
+                torch.cuda.empty_cache()
+
+
 ALL = {"offload": bench_offload, "mixtral": bench_mixtral,
+       "weight_tiers": bench_weight_tiers,
        "mixtral_w4": lambda: bench_mixtral(quantize_q4=True),
        "families": bench_families,
        "kv_multiplex": bench_kv_multiplex,

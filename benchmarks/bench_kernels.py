@@ -597,6 +597,62 @@ def bench_w4_tiled():
         del ws
 
 
+def bench_w8():
+    """The fp8 (e4m3) weight tier's decode GEMM (gemm_w8.hip) at the
+    llama-3-8b projections, M = 1, 8, 32: hip_w8.gemm_w8 at its own plan and
+    cache policy, the row-quantise launch on its own, and beside them on the
+    same weight ops.linear with the packed bf16 copy and ops.linear_w4. Each
+    path cycles through enough copies of its weight that a call never finds
+    it in the 256 MB last-level cache; three alternating rounds per point,
+    median of medians. TB/s is the fp8 codes over the kernel's time.
+    BBAMD_BENCH_W8_KSPLIT="1,2,4" adds gemm_w8 at those forced splits and
+    both cache policies."""
+    forced = [int(s) for s in os.environ.get("BBAMD_BENCH_W8_KSPLIT", "").split(",") if s]
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    for N, K, tag in [(6144, 4096, "qkv"), (4096, 4096, "o"),
+                      (28672, 4096, "gate_up"), (4096, 14336, "down")]:
+        wb = torch.randn(N, K, generator=gen, device=DEV,
+                         dtype=torch.float32).mul_(K ** -0.5).to(torch.bfloat16)
+        codes, w_scale = ops.quant_w8(wb)
+        nrot = max(2, -(-(512 << 20) // (N * K)))
+        w8s = [ops.pack_w8(codes) for _ in range(nrot)]
+        w16 = [(wb.clone(), ops.pack_skinny_w(wb)) for _ in range(nrot)]
+        w4s = [ops.quant4_pack(wb) for _ in range(nrot)]
+        for M in (1, 8, 32):
+            a = torch.randn(M, K, generator=gen, device=DEV,
+                            dtype=torch.float32).to(torch.bfloat16)
+            a8, a_scale = ops.hip_w8.quant_rows_fp8(a)
+            i = [0]
+
+            def w8(ks=0, nt=0):
+                i[0] += 1
+                return ops.hip_w8.gemm_w8(a8, a_scale, w8s[i[0] % nrot], w_scale,
+                                          None, None, N, ks, nt)
+
+            def bf16():
+                i[0] += 1
+                w, wp = w16[i[0] % nrot]
+                return ops.linear(a, w, w_packed=wp)
+
+            def w4():
+                i[0] += 1
+                p, s, z = w4s[i[0] % nrot]
+                return ops.linear_w4(a, p, s, z, N)
+
+            fns = (w8, lambda: ops.hip_w8.quant_rows_fp8(a), bf16, w4)
+            rounds = [[_event_time(f, 30, 5) for f in fns] for _ in range(3)]
+            ts = [sorted(r[j] for r in rounds)[1] for j in range(len(fns))]
+            extra = "".join(
+                f"  ks={ks},nt={nt} {_event_time(lambda: w8(ks, nt), 30, 5)*1e6:.1f}"
+                for ks in forced for nt in (-1, 1))
+            plan = tuple(ops.hip_w8.gemm_w8_plan(N, K, 0))
+            print(f"w8 {tag} N{N} K{K} M{M} plan {plan}: gemm_w8 {ts[0]*1e6:6.1f} us "
+                  f"{N*K/ts[0]/1e12:5.2f} TB/s  quant_rows {ts[1]*1e6:5.1f} us  "
+                  f"bf16 packed {ts[2]*1e6:6.1f} us  linear_w4 {ts[3]*1e6:6.1f} us  "
+                  f"bf16/(w8+quant) {ts[2]/(ts[0]+ts[1]):5.2f}{extra}", flush=True)
+        del w8s, w16, w4s
+
+
 ALL = {
     "attn_decode": bench_attn_decode,
     "attn_decode_fp8": bench_attn_decode_fp8,
@@ -613,6 +669,7 @@ ALL = {
     "gemm_norm": bench_gemm_norm,
     "moe_w4": bench_moe_w4,
     "w4_tiled": bench_w4_tiled,
+    "w8": bench_w8,
 }
 
 if __name__ == "__main__":

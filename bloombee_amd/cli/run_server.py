@@ -78,12 +78,14 @@ def main():
                     choices=["bfloat16", "float32"],
                     help="serve dtype (kernels are bf16; float32 = CPU path)")
     ap.add_argument("--quant-type", default="none",
-                    choices=["none", "nf4", "w4"],
+                    choices=["none", "nf4", "w4", "w8"],
                     help="nf4 maps to the 4-bit host weight tier "
                          "(compress_weight); w4 quantizes the resident "
                          "weights and decodes through the 4-bit weight-stream "
                          "kernels (llama, qwen3, mixtral; not with weight "
-                         "offload); LLM.int8 is not supported")
+                         "offload); w8 quantizes them to fp8 (e4m3) and "
+                         "decodes through the fp8-MFMA kernel (llama, qwen3; "
+                         "not with weight offload); LLM.int8 is not supported")
     args = ap.parse_args()
 
     if args.max_chunk_tokens is not None:
@@ -131,6 +133,7 @@ def main():
         announce_port=args.announce_port,
         quantize_q4=args.quant_type == "w4",
         kv_dtype=args.kv_dtype,
+        quantize_fp8=args.quant_type == "w8",
     )
     server.run()
 

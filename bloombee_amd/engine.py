@@ -124,7 +124,8 @@ class LocalEngine:
     """
 
     def __init__(self, config_or_name, device="cpu", seed: int = 0,
-                 kv_max_tokens: int = 1 << 16, quantize_q4: bool = False):
+                 kv_max_tokens: int = 1 << 16, quantize_q4: bool = False,
+                 quantize_fp8: bool = False):
         cfg = (config_or_name if isinstance(config_or_name, ModelConfig)
                else resolve_config(config_or_name))
         self.config = cfg
@@ -157,6 +158,19 @@ class LocalEngine:
             for blk in self.stack.blocks:
                 if hasattr(blk, "quantize_weights_q4"):
                     blk.quantize_weights_q4()
+        if quantize_fp8:
+            # opt-in fp8 (e4m3) weight tier (gemm_w8.hip): W8A8 decode GEMMs
+            # that stream half the bf16 bytes
+            if quantize_q4:
+                raise ValueError("quantize_fp8 and quantize_q4 are two weight "
+                                 "tiers: pick one")
+            for blk in self.stack.blocks:
+                if not hasattr(blk, "quantize_weights_fp8"):
+                    raise ValueError(
+                        f"quantize_fp8: model family {cfg.model_type!r} has "
+                        "no fp8 weight path (llama and qwen3 have one)")
+            for blk in self.stack.blocks:
+                blk.quantize_weights_fp8()
         self.kv_pool = self.stack.make_kv(kv_max_tokens)
 
     @torch.no_grad()

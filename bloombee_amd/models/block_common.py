@@ -229,6 +229,9 @@ def pack_q4(block: torch.nn.Module, names, keep_full: bool = False) -> None:
     stacked weights keep their leading dimensions) as block._w4[name] =
     (packed, scale, zero, N). keep_full=False drops the bf16 weights: the
     block becomes inference-only."""
+    if getattr(block, "_w8", None) is not None:
+        raise RuntimeError("block already holds fp8 weights "
+                           "(quantize_weights_fp8): one weight tier per block")
     block._w4 = {}
     for name in names:
         w = getattr(block, name).detach()
@@ -238,6 +241,31 @@ def pack_q4(block: torch.nn.Module, names, keep_full: bool = False) -> None:
                            scale.reshape(*lead, -1).half().contiguous(),
                            zero.reshape(*lead, -1).half().contiguous(),
                            w.shape[-2])
+        if not keep_full:
+            getattr(block, name).data = torch.empty(
+                0, dtype=w.dtype, device=w.device)
+
+
+# ----------------------------------------------------------------------
+# fp8 (e4m3) weights
+# ----------------------------------------------------------------------
+@torch.no_grad()
+def pack_w8(block: torch.nn.Module, names, keep_full: bool = False) -> None:
+    """Quantise the named (N, K) weights to e4m3 codes with a power-of-two
+    scale per output row, stored tiled in the W8 kernel's read order only
+    (ops.pack_w8), as block._w8[name] = (packed, w_scale, N).
+    keep_full=False drops the bf16 weights: the block becomes
+    inference-only. A block takes one tier, once."""
+    if (getattr(block, "_w8", None) is not None
+            or getattr(block, "_w4", None) is not None):
+        raise RuntimeError("block weights are already quantized "
+                           "(quantize_weights_fp8 / quantize_weights_q4): "
+                           "one weight tier per block, packed once")
+    block._w8 = {}
+    for name in names:
+        w = getattr(block, name).detach()
+        codes, w_scale = ops.quant_w8(w)
+        block._w8[name] = (ops.pack_w8(codes), w_scale.contiguous(), w.shape[0])
         if not keep_full:
             getattr(block, name).data = torch.empty(
                 0, dtype=w.dtype, device=w.device)

@@ -31,7 +31,7 @@ from bloombee_amd import ops
 from bloombee_amd.kv.paged import SessionHandle
 from bloombee_amd.models.base import ModelConfig
 from bloombee_amd.models.block_common import (  # noqa: F401 (RopeTables: re-export)
-    FamilyBlock, RopeTables, pack_q4, paged_attention_qkv, rms_train,
+    FamilyBlock, RopeTables, pack_q4, pack_w8, paged_attention_qkv, rms_train,
     rope_attn_train, rotary_positions, split_heads, swiglu_mlp_train)
 
 
@@ -130,8 +130,9 @@ class LlamaBlock(FamilyBlock):
     def _fuse_norm_gate(self, hidden) -> bool:
         """All four decode GEMMs must hit the v2 kernel (K%256) with
         stripe-aligned N so the fused-norm ss chain stays on-device;
-        W4/LoRA blocks keep the separate-norm path."""
+        W4/W8/LoRA blocks keep the separate-norm path."""
         return (getattr(self, "_w4", None) is None
+                and getattr(self, "_w8", None) is None
                 and getattr(self, "lora_delta", None) is None
                 and ops.fuse_norm_linear_ok(hidden, self.qkv_w)
                 and self.I % 256 == 0 and (2 * self.I) % 64 == 0
@@ -203,14 +204,32 @@ class LlamaBlock(FamilyBlock):
         pack_q4(self, ("qkv_w", "o_w", "gate_up_w", "down_w"), keep_full)
         return self
 
+    @torch.no_grad()
+    def quantize_weights_fp8(self, keep_full: bool = False):
+        """Quantise the four projection weights to fp8 (e4m3) codes with a
+        power-of-two scale per output row, kept only as the tiled copy the
+        W8 decode kernel streams (gemm_w8.hip): half the bf16 bytes, the
+        activation quantised per token to e4m3 too (W8A8, ops.linear_w8).
+        keep_full=False drops the bf16 weights (the block becomes
+        inference-only). Above 32 rows ops.linear_w8 composes the same
+        definition from torch ops. Raises on a block that is already
+        quantized, in either tier."""
+        self._drop_packed()
+        pack_w8(self, ("qkv_w", "o_w", "gate_up_w", "down_w"), keep_full)
+        return self
+
     def _lin(self, x, w, name, **kw):
         """ops.linear + optional active-LoRA delta (utils/peft.py).
-        Quantized blocks (quantize_weights_q4) route through the 4-bit
-        weight-stream kernel instead."""
+        Quantized blocks (quantize_weights_q4 / quantize_weights_fp8) route
+        through their tier's weight-stream kernel instead."""
         w4 = getattr(self, "_w4", None)
+        w8 = getattr(self, "_w8", None)
         if w4 is not None and name in w4:
             packed, scale, zero, N = w4[name]
             y = ops.linear_w4(x, packed, scale, zero, N, **kw)
+        elif w8 is not None and name in w8:
+            packed, w_scale, N = w8[name]
+            y = ops.linear_w8(x, packed, w_scale, N, **kw)
         else:
             y = ops.linear(x, w, **kw)
         ld = getattr(self, "lora_delta", None)
@@ -257,8 +276,9 @@ class LlamaBlock(FamilyBlock):
         if fuse_norm and not getattr(self, "_norm_folded", False):
             self.fold_norm_weights()   # one-time reparameterization
         if self._wpacked and (getattr(self, "_w4", None) is not None
+                              or getattr(self, "_w8", None) is not None
                               or getattr(self, "lora_delta", None) is not None):
-            self._drop_packed()        # W4 / LoRA closed the gate for good
+            self._drop_packed()        # W4 / W8 / LoRA closed the gate for good
         pb = getattr(self, "prev_block", None)
         # the qkv GEMM's split-K combine folds into rope_kv_write: the GEMM
         # hands over its f32 slabs and the combine launch disappears

@@ -158,7 +158,21 @@ __host__ __device__ inline long skinny_packed_offset(int g, int kb, int K) {
   return ((long)g * (K / 32) + kb) * SKINNY_PACK_BLOCK;
 }
 
-#define HIP_OK(expr)                                                         \
+// Pre-tiled fp8 (e4m3) weight of the W8 decode GEMM (gemm_w8.hip), for codes
+// (N, K) with N % 16 == 0 and K % 128 == 0 (mirrored by pack_w8 in
+// ops/reference.py):
+//   Wp[g][kb][h][q][li][e] = codes[g*16 + li][kb*128 + q*32 + h*16 + e]
+// with g < N/16, kb < K/128, h < 2, q < 4, li < 16, e < 16. One (g, kb) tile
+// is 16 rows x 128 k = 2 KB in two lane-linear 1 KB halves: lane q*16 + li
+// owns the 16 bytes at h*1024 + lane*16 of half h. Each of a tile's two wave
+// loads is one contiguous 1 KB, and a lane's 32 bytes (k = q*32 .. q*32 + 31
+// of row li) are its operand of one 16x16x128 fp8 MFMA as they arrive.
+static constexpr int W8_TILE_BYTES = 2048;
+__host__ __device__ inline long w8_packed_offset(int g, int kb, int K) {
+  return ((long)g * (K / 128) + kb) * W8_TILE_BYTES;
+}
+
+#define HIP_OK(expr)                                                        \
   do {                                                                       \
     hipError_t _e = (expr);                                                  \
     if (_e != hipSuccess) {                                                  \

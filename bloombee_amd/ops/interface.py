@@ -23,9 +23,11 @@ logger = get_logger(__name__)
 
 try:
     hip_ops = importlib.import_module("bloombee_amd.ops._hip_ops")
+    # the fp8 weight tier's bindings (ops/hip/w8_ext.hip), a module of its own
+    hip_w8 = importlib.import_module("bloombee_amd.ops._hip_w8")
     HAVE_HIP_OPS = True
 except ImportError as e:  # pragma: no cover
-    hip_ops = None
+    hip_ops = hip_w8 = None
     HAVE_HIP_OPS = False
     _import_error = e
 
@@ -861,6 +863,52 @@ def linear_w4(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor,
     if residual is not None:
         y = y + residual.view_as(y)
     return y
+
+
+# ---------------------------------------------------------------------------
+# fp8 (e4m3) weight tier (W8A8); the definition is reference.linear_w8
+# ---------------------------------------------------------------------------
+def quant_w8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """w (N, K) -> codes (N, K) e4m3 and w_scale (N,) f32, a power of two per
+    output row. Runs once per weight, as torch expressions on w's device."""
+    return ref.quant_w8(w)
+
+
+def pack_w8(codes: torch.Tensor) -> torch.Tensor:
+    """The tiled copy of codes (N, K) that linear_w8 streams: 2 KB tiles in
+    the W8 kernel's read order (ops/hip/common.h, w8_packed_offset)."""
+    return ref.pack_w8(codes)
+
+
+def unpack_w8(packed: torch.Tensor) -> torch.Tensor:
+    return ref.unpack_w8(packed)
+
+
+def linear_w8(x: torch.Tensor, packed: torch.Tensor, w_scale: torch.Tensor,
+              N: int, residual: Optional[torch.Tensor] = None,
+              bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = a_scale * w_scale * (a8 @ codes^T) (+bias) (+residual): x is
+    quantised per row to e4m3 (a8, a_scale), `packed` is pack_w8 of the
+    weight's codes, all scales are powers of two (reference.linear_w8).
+    On the GPU, bf16 x of at most 32 rows with K % 128 == 0 and N % 64 == 0
+    runs the row quantiser and the fp8-MFMA weight-stream kernel
+    (gemm_w8.hip), half the bf16 kernel's bytes. Everything else on the GPU
+    (more rows, odd shapes) and BBAMD_W8_KERNEL=0 (read per call) is the same
+    definition composed from torch ops: quantise the rows, un-tile, matmul
+    in f32; only its last-ulp rounding may differ from the kernel's. The CPU
+    runs the reference."""
+    K = x.shape[-1]
+    M = x.numel() // K
+    if not _on_gpu(x):
+        return ref.linear_w8(x, ref.unpack_w8(packed), w_scale, residual, bias)
+    if (x.dtype == torch.bfloat16 and 1 <= M <= 32 and K % 128 == 0
+            and N % 64 == 0 and os.environ.get("BBAMD_W8_KERNEL", "1") != "0"):
+        _require_ext()
+        a8, a_scale = hip_w8.quant_rows_fp8(x.contiguous())
+        if residual is not None:
+            residual = residual.contiguous()
+        return hip_w8.gemm_w8(a8, a_scale, packed, w_scale, residual, bias, N)
+    return ref.linear_w8(x, ref.unpack_w8(packed), w_scale, residual, bias)
 
 
 def quant4_pack(x: torch.Tensor, group_size: int = 64):

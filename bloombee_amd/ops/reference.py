@@ -560,6 +560,77 @@ def unpack_skinny_w(wp: torch.Tensor, swiglu: bool = False) -> torch.Tensor:
     return w
 
 
+# ---------------------------------------------------------------------------
+# fp8 (e4m3) weight tier, W8A8 (ops/hip/gemm_w8.hip). Every scale is a power
+# of two, so scaling is exact and each value is rounded once.
+# ---------------------------------------------------------------------------
+FP8 = torch.float8_e4m3fn
+
+
+def _quant_rows_e4m3(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per row of x (R, K): scale 2^e with the smallest integer e such that
+    amax / 2^e <= 448 (1 for a zero row) and codes e4m3_rne(x / scale)."""
+    xd = x.double()
+    amax = xd.abs().amax(dim=-1)
+    m, ex = torch.frexp(amax)                       # amax = m * 2^ex, m in [.5, 1)
+    e = ex - 9 + (m > 0.875).int()                  # 448 = 0.875 * 2^9
+    scale = torch.where(amax == 0, torch.ones_like(amax),
+                        torch.ldexp(torch.ones_like(amax), e))
+    codes = (xd / scale.unsqueeze(-1)).float().to(FP8)
+    return codes, scale.float()
+
+
+def quant_w8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """w (N, K) -> codes (N, K) e4m3, w_scale (N,) f32: one scale per output
+    row."""
+    assert w.dim() == 2
+    return _quant_rows_e4m3(w)
+
+
+def quant_rows_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x (..., K) -> a8 (..., K) e4m3, a_scale (rows,) f32: the same rule per
+    row (token) of the activation."""
+    a8, a_scale = _quant_rows_e4m3(x.reshape(-1, x.shape[-1]))
+    return a8.view(x.shape), a_scale
+
+
+def pack_w8(codes: torch.Tensor) -> torch.Tensor:
+    """codes (N, K) e4m3 -> Wp[g][kb][h][q][li][e] = codes[g*16 + li][kb*128
+    + q*32 + h*16 + e], shape (N/16, K/128, 2, 4, 16, 16): the order
+    gemm_w8_kernel's lanes read it in (ops/hip/common.h, w8_packed_offset)."""
+    N, K = codes.shape
+    assert N % 16 == 0 and K % 128 == 0, "tiled fp8 W needs N%16, K%128"
+    return (codes.view(torch.uint8)
+            .reshape(N // 16, 16, K // 128, 4, 2, 16)   # [g, li, kb, q, h, e]
+            .permute(0, 2, 4, 3, 1, 5).contiguous().view(FP8))
+
+
+def unpack_w8(wp: torch.Tensor) -> torch.Tensor:
+    """Inverse of pack_w8: a permuted view, made row-major (N, K)."""
+    G, KB = wp.shape[0], wp.shape[1]
+    return (wp.view(torch.uint8).permute(0, 4, 1, 3, 2, 5)
+            .reshape(G * 16, KB * 128).view(FP8))
+
+
+def linear_w8(x: torch.Tensor, codes: torch.Tensor, w_scale: torch.Tensor,
+              residual: Optional[torch.Tensor] = None,
+              bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[m, n] = a_scale[m] * w_scale[n] * sum_k a8[m, k] * codes[n, k]
+    (+bias) (+residual), summed in f32, rounded once to x.dtype. The
+    activation is quantised per row here (quant_rows_fp8): the one definition
+    of the tier on every path."""
+    a8, a_scale = quant_rows_fp8(x)
+    K = x.shape[-1]
+    y = a8.reshape(-1, K).float() @ codes.float().t()
+    y = y * a_scale.unsqueeze(1) * w_scale.float().unsqueeze(0)
+    if bias is not None:
+        y = y + bias.float()
+    y = y.view(*x.shape[:-1], -1)
+    if residual is not None:
+        y = y + residual.float().view_as(y)
+    return y.to(x.dtype)
+
+
 def xcd_remap(b: int, nwg: int) -> int:
     """Tile that block b of a grid row of nwg blocks works on (ops/hip/
     common.h, xcd_remap): the dispatcher puts block b on XCD b % 8, the remap

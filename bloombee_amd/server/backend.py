@@ -41,10 +41,19 @@ class StackBackend:
                  offload_policy=None,
                  max_batch_size: int = 2048,
                  quantize_q4: bool = False,
-                 kv_dtype: Optional[str] = None):
+                 kv_dtype: Optional[str] = None,
+                 quantize_fp8: bool = False):
         self.config = config
         self.start, self.end = start, end
         self.device = torch.device(device)
+        if quantize_fp8 and quantize_q4:
+            raise ValueError("quantize_fp8 and quantize_q4 are two weight "
+                             "tiers: pick one")
+        if (quantize_fp8 and offload_policy is not None
+                and offload_policy.offloads_weights):
+            raise ValueError(
+                "quantize_fp8 cannot be combined with weight offload: the "
+                "offload arena copies bf16 tensors")
         if (quantize_q4 and offload_policy is not None
                 and offload_policy.offloads_weights):
             raise ValueError(
@@ -66,6 +75,15 @@ class StackBackend:
                         "no 4-bit compute path")
             for blk in self.stack.blocks:
                 blk.quantize_weights_q4()
+        if quantize_fp8:
+            # compute-path fp8 (e4m3) weights (gemm_w8.hip), refused like W4
+            for blk in self.stack.blocks:
+                if not hasattr(blk, "quantize_weights_fp8"):
+                    raise ValueError(
+                        f"quantize_fp8: model family {config.model_type!r} "
+                        "has no fp8 weight path (llama and qwen3 have one)")
+            for blk in self.stack.blocks:
+                blk.quantize_weights_fp8()
         if offload_policy is not None and offload_policy.offloads_weights:
             from bloombee_amd.offload.weights import OffloadedBlockStack
             self.stack = OffloadedBlockStack(self.stack, offload_policy)

@@ -57,6 +57,7 @@ class Server:
         announce_port: Optional[int] = None,
         quantize_q4: bool = False,
         kv_dtype: Optional[str] = None,
+        quantize_fp8: bool = False,
     ):
         self.config = model if isinstance(model, ModelConfig) else resolve_config(model)
         self.model_name = model_name or (model if isinstance(model, str)
@@ -117,7 +118,8 @@ class Server:
                                 offload_policy=offload_policy,
                                 max_batch_size=max_batch_size,
                                 quantize_q4=quantize_q4,
-                                kv_dtype=kv_dtype)
+                                kv_dtype=kv_dtype,
+                                quantize_fp8=quantize_fp8)
         self.backend = StackBackend(self.config, block_indices[0],
                                     block_indices[1], **self._backend_kw)
         if adapters:

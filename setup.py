@@ -17,6 +17,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent
 HIP_DIR = ROOT / "bloombee_amd" / "ops" / "hip"
 OUT_SO = ROOT / "bloombee_amd" / "ops" / "_hip_ops.so"
+W8_SO = ROOT / "bloombee_amd" / "ops" / "_hip_w8.so"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 
@@ -27,9 +28,56 @@ def torch_paths():
     return tdir / "include", tdir / "lib"
 
 
+def _torch_ext_flags(name: str) -> list:
+    tinc, _ = torch_paths()
+    return [
+        "-I", str(tinc),
+        "-I", str(tinc / "torch" / "csrc" / "api" / "include"),
+        "-I", "/opt/rocm/include",
+        "-I", sysconfig.get_paths()["include"],
+        "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1", "-DHIPBLAS_V2",
+        "-DCUDA_HAS_FP16=1", "-D__HIP_NO_HALF_OPERATORS__=1",
+        "-D__HIP_NO_HALF_CONVERSIONS__=1", "-DHIP_ENABLE_WARP_SYNC_BUILTINS=1",
+        "-DTORCH_API_INCLUDE_EXTENSION_H", f"-DTORCH_EXTENSION_NAME={name}",
+    ]
+
+
+def _link(objs, out: Path) -> list:
+    _, tlib = torch_paths()
+    return [
+        "g++", "-shared", *map(str, objs),
+        "-L", str(tlib), "-L", "/opt/rocm/lib",
+        "-lc10", "-ltorch", "-ltorch_cpu", "-ltorch_python",
+        "-lamdhip64", "-lc10_hip", "-ltorch_hip", "-lz",
+        "-o", str(out),
+    ]
+
+
+def _run(cmds, verbose: bool) -> None:
+    for cmd in cmds:
+        if verbose:
+            print("+", " ".join(cmd), file=sys.stderr)
+        subprocess.run(cmd, check=True)
+
+
+def build_w8(verbose: bool = True) -> Path:
+    """_hip_w8.so: the fp8 (e4m3) weight tier, bindings (w8_ext.hip) and
+    kernels (gemm_w8.hip) in one translation unit, built without packed-fp32
+    instructions."""
+    obj = HIP_DIR / "w8_ext.o"
+    compile_cmd = [
+        "/opt/rocm/bin/hipcc", f"--offload-arch={ARCH}",
+        "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
+        "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
+        *_torch_ext_flags("_hip_w8"),
+        "-c", str(HIP_DIR / "w8_ext.hip"), "-o", str(obj),
+    ]
+    _run((compile_cmd, _link([obj], W8_SO)), verbose)
+    obj.unlink(missing_ok=True)
+    return W8_SO
+
+
 def build(verbose: bool = True) -> Path:
-    tinc, tlib = torch_paths()
-    py_inc = sysconfig.get_paths()["include"]
     src = HIP_DIR / "ext.hip"
     obj = HIP_DIR / "ext.o"
     # the fp8 KV kernels are a translation unit of their own (raw-pointer
@@ -46,30 +94,13 @@ def build(verbose: bool = True) -> Path:
         "-I", "/opt/rocm/include", "-D__HIP_PLATFORM_AMD__=1",
         "-c", str(kv8_src), "-o", str(kv8_obj),
     ]
-    compile_cmd = hipcc + [
-        "-I", str(tinc),
-        "-I", str(tinc / "torch" / "csrc" / "api" / "include"),
-        "-I", "/opt/rocm/include",
-        "-I", py_inc,
-        "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1", "-DHIPBLAS_V2",
-        "-DCUDA_HAS_FP16=1", "-D__HIP_NO_HALF_OPERATORS__=1",
-        "-D__HIP_NO_HALF_CONVERSIONS__=1", "-DHIP_ENABLE_WARP_SYNC_BUILTINS=1",
-        "-DTORCH_API_INCLUDE_EXTENSION_H", "-DTORCH_EXTENSION_NAME=_hip_ops",
+    compile_cmd = hipcc + _torch_ext_flags("_hip_ops") + [
         "-c", str(src), "-o", str(obj),
     ]
-    link_cmd = [
-        "g++", "-shared", str(obj), str(kv8_obj),
-        "-L", str(tlib), "-L", "/opt/rocm/lib",
-        "-lc10", "-ltorch", "-ltorch_cpu", "-ltorch_python",
-        "-lamdhip64", "-lc10_hip", "-ltorch_hip", "-lz",
-        "-o", str(OUT_SO),
-    ]
-    for cmd in (compile_cmd, kv8_cmd, link_cmd):
-        if verbose:
-            print("+", " ".join(cmd), file=sys.stderr)
-        subprocess.run(cmd, check=True)
+    _run((compile_cmd, kv8_cmd, _link([obj, kv8_obj], OUT_SO)), verbose)
     obj.unlink(missing_ok=True)
     kv8_obj.unlink(missing_ok=True)
+    build_w8(verbose)
     return OUT_SO
 
 
