@@ -335,18 +335,41 @@ def bench_families(steps=24):
             print(json.dumps({"family_bench": name, "error": str(e)[:200]}))
 
 
-def bench_weight_tiers(steps=48, B=32, prompt=2048):
+def _prefill_ms(eng, B, T, reps=3):
+    """Median wall time of `reps` prefills of B prompts of T tokens (ms),
+    after one that is not timed."""
+    ids = torch.randint(0, eng.config.vocab_size, (B, T),
+                        generator=torch.Generator().manual_seed(0))
+    ts = []
+    for _ in range(reps + 1):
+        kv = eng.kv_pool.allocate(B, T + 4)
+        if DEV.startswith("cuda"):
+            torch.cuda.synchronize()
+        t0 = time.monotonic()
+        eng.prefill(ids, kv)
+        if DEV.startswith("cuda"):
+            torch.cuda.synchronize()
+        ts.append((time.monotonic() - t0) * 1000)
+        kv.close()
+    return sorted(ts[1:])[reps // 2]
+
+
+def bench_weight_tiers(steps=48, B=32, prompt=2048, decode=True):
     """Flagship decode (llama-3-8b, batch 32, 2k prompt) through LocalEngine
     per weight tier: the default bf16 path, quantize_fp8 (gemm_w8.hip) and
-    quantize_q4, one engine at a time in one process, two rounds each."""
+    quantize_q4, one engine at a time in one process, two rounds each. Then
+    prefill per tier, a 2k-token prompt at batch 1 and 512-token prompts at
+    batch 4: bf16, fp8 with the tiled kernel (gemm_w8_tiled.hip) and fp8
+    under BBAMD_W8_TILED=0 (the torch composition). decode=False runs the
+    prefill figures alone."""
     from bloombee_amd.engine import LocalEngine
 
     tiers = (("bf16", {}), ("fp8", {"quantize_fp8": True}),
              ("w4", {"quantize_q4": True}))
-    for rnd in range(2):
+    model = "llama-3-8b" if DEV != "cpu" else "llama-tiny"
+    for rnd in range(2 if decode else 0):
         for tag, kw in tiers:
-            eng = LocalEngine("llama-3-8b" if DEV != "cpu" else "llama-tiny",
-                              device=DEV, seed=0,
+            eng = LocalEngine(model, device=DEV, seed=0,
                               kv_max_tokens=B * (prompt + steps + 32) + 1024, **kw)
             tps, ms = _decode_loop(eng, B, prompt, steps)
             print(json.dumps({"weight_tier": tag, "round": rnd, "batch": B,
@@ -355,6 +378,23 @@ def bench_weight_tiers(steps=48, B=32, prompt=2048):
             del eng
             if DEV.startswith("cuda"):
                 torch.cuda.empty_cache()
+    for tag, kw in tiers[:2]:
+        eng = LocalEngine(model, device=DEV, seed=0, kv_max_tokens=8192, **kw)
+        for rnd in range(2):
+            for tiled in ("1", "0") if tag == "fp8" else ("1",):
+                os.environ["BBAMD_W8_TILED"] = tiled
+                for pb, pt in ((1, 2048), (4, 512)):
+                    ms = _prefill_ms(eng, pb, pt)
+                    print(json.dumps({
+                        "weight_tier": tag if tiled == "1" else tag + "-composed",
+                        "round": rnd, "batch": pb, "prompt": pt,
+                        "prefill_ms": round(ms, 2),
+                        "prefill_tokens_per_s": round(pb * pt / ms * 1000, 1)}),
+                        flush=True)
+        os.environ.pop("BBAMD_W8_TILED", None)
+        del eng
+        if DEV.startswith("cuda"):
+            torch.cuda.empty_cache()
 
 
 ALL = {"offload": bench_offload, "mixtral": bench_mixtral,

@@ -653,6 +653,76 @@ def bench_w8():
         del w8s, w16, w4s
 
 
+def bench_w8_tiled():
+    """The fp8 weight tier above 32 rows (gemm_w8_tiled.hip) at the llama-3-8b
+    projections, M = 64 .. 4096: (a) quant_rows_fp8 + gemm_w8_tiled as
+    ops.linear_w8 runs them, and the GEMM alone; (b) the parent's path,
+    ops.linear_w8 under BBAMD_W8_TILED=0 (torch composition); (c) for
+    information ops.linear on the bf16 weight. Three alternating rounds per
+    point, median of 30 device-event times each, median round and spread;
+    every path cycles through >= 512 MB of weight copies. TF/s is 2 M N K
+    and TB/s the fp8 codes over the GEMM's time; `bound` names the larger of
+    the two as fractions of 5 PF/s fp8 and 8 TB/s; `plan` is (BM, m-tiles,
+    ksplit, kchunk). BBAMD_BENCH_W8_KSPLIT="1,2,4" adds the GEMM at those
+    forced splits."""
+    forced = [int(s) for s in os.environ.get("BBAMD_BENCH_W8_KSPLIT", "").split(",") if s]
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    for N, K, tag in [(6144, 4096, "qkv"), (4096, 4096, "o"),
+                      (28672, 4096, "gate_up"), (4096, 14336, "down")]:
+        wb = torch.randn(N, K, generator=gen, device=DEV,
+                         dtype=torch.float32).mul_(K ** -0.5).to(torch.bfloat16)
+        codes, w_scale = ops.quant_w8(wb)
+        nrot = max(2, -(-(512 << 20) // (N * K)))
+        w8s = [ops.pack_w8(codes) for _ in range(nrot)]
+        w16 = [wb.clone() for _ in range((nrot + 1) // 2)]
+        del codes
+        for M in (64, 128, 256, 512, 1024, 2048, 4096):
+            a = torch.randn(M, K, generator=gen, device=DEV,
+                            dtype=torch.float32).to(torch.bfloat16)
+            a8, a_scale = ops.hip_w8.quant_rows_fp8(a)
+            i = [0]
+
+            def gemm(ks=0):
+                i[0] += 1
+                return ops.hip_w8.gemm_w8_tiled(a8, a_scale, w8s[i[0] % nrot],
+                                                w_scale, None, None, N, ks)
+
+            def entry():
+                i[0] += 1
+                return ops.linear_w8(a, w8s[i[0] % nrot], w_scale, N)
+
+            def kernel():
+                os.environ["BBAMD_W8_TILED"] = "1"
+                return entry()
+
+            def parent():
+                os.environ["BBAMD_W8_TILED"] = "0"
+                return entry()
+
+            def bf16():
+                i[0] += 1
+                return ops.linear(a, w16[i[0] % len(w16)])
+
+            fns = (kernel, gemm, parent, bf16)
+            rounds = [[_event_time(f, 30, 3) for f in fns] for _ in range(3)]
+            os.environ.pop("BBAMD_W8_TILED", None)
+            lo, ts, hi = ([sorted(r[j] for r in rounds)[q] for j in range(len(fns))]
+                          for q in range(3))
+            extra = "".join(f"  ks={ks} {_event_time(lambda: gemm(ks), 30, 3)*1e6:.1f} us"
+                            for ks in forced)
+            tf, tb = 2.0 * M * N * K / ts[1] / 1e12, N * K / ts[1] / 1e12
+            plan = tuple(ops.hip_w8.gemm_w8_tiled_plan(M, N, K, 0))
+            print(f"w8_tiled {tag} N{N} K{K} M{M} plan {plan}: "
+                  f"quant+gemm {ts[0]*1e6:8.1f} us [{lo[0]*1e6:.1f}..{hi[0]*1e6:.1f}]  "
+                  f"gemm {ts[1]*1e6:8.1f} us {tf:7.1f} TF/s {tb:5.2f} TB/s "
+                  f"bound {'mfma' if tf / 5000 > tb / 8 else 'stream'}   "
+                  f"composition {ts[2]*1e6:9.1f} us [{lo[2]*1e6:.1f}..{hi[2]*1e6:.1f}]   "
+                  f"bf16 library {ts[3]*1e6:8.1f} us   "
+                  f"parent/kernel {ts[2]/ts[0]:6.2f}  bf16/kernel {ts[3]/ts[0]:5.2f}{extra}",
+                  flush=True)
+        del w8s, w16
+
+
 ALL = {
     "attn_decode": bench_attn_decode,
     "attn_decode_fp8": bench_attn_decode_fp8,
@@ -670,6 +740,7 @@ ALL = {
     "moe_w4": bench_moe_w4,
     "w4_tiled": bench_w4_tiled,
     "w8": bench_w8,
+    "w8_tiled": bench_w8_tiled,
 }
 
 if __name__ == "__main__":

@@ -208,11 +208,11 @@ class LlamaBlock(FamilyBlock):
     def quantize_weights_fp8(self, keep_full: bool = False):
         """Quantise the four projection weights to fp8 (e4m3) codes with a
         power-of-two scale per output row, kept only as the tiled copy the
-        W8 decode kernel streams (gemm_w8.hip): half the bf16 bytes, the
-        activation quantised per token to e4m3 too (W8A8, ops.linear_w8).
-        keep_full=False drops the bf16 weights (the block becomes
-        inference-only). Above 32 rows ops.linear_w8 composes the same
-        definition from torch ops. Raises on a block that is already
+        W8 kernels read (gemm_w8.hip up to 32 rows, gemm_w8_tiled.hip above:
+        prefill, chunked prefill, tree verify, large-batch decode): half the
+        bf16 bytes, the activation quantised per token to e4m3 too (W8A8,
+        ops.linear_w8). keep_full=False drops the bf16 weights (the block
+        becomes inference-only). Raises on a block that is already
         quantized, in either tier."""
         self._drop_packed()
         pack_w8(self, ("qkv_w", "o_w", "gate_up_w", "down_w"), keep_full)

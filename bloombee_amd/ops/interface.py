@@ -890,24 +890,28 @@ def linear_w8(x: torch.Tensor, packed: torch.Tensor, w_scale: torch.Tensor,
     """y = a_scale * w_scale * (a8 @ codes^T) (+bias) (+residual): x is
     quantised per row to e4m3 (a8, a_scale), `packed` is pack_w8 of the
     weight's codes, all scales are powers of two (reference.linear_w8).
-    On the GPU, bf16 x of at most 32 rows with K % 128 == 0 and N % 64 == 0
-    runs the row quantiser and the fp8-MFMA weight-stream kernel
-    (gemm_w8.hip), half the bf16 kernel's bytes. Everything else on the GPU
-    (more rows, odd shapes) and BBAMD_W8_KERNEL=0 (read per call) is the same
+    On the GPU, bf16 x with K % 128 == 0 and N % 64 == 0 runs the row
+    quantiser and an fp8-MFMA kernel over the same tiled codes: up to 32 rows
+    the weight-stream kernel (gemm_w8.hip), above 32 rows (prefill, chunked
+    prefill, tree verify, large-batch decode) the tiled kernel
+    (gemm_w8_tiled.hip). Odd shapes, BBAMD_W8_KERNEL=0 (the whole tier) and
+    BBAMD_W8_TILED=0 (above 32 rows only; both read per call) run the same
     definition composed from torch ops: quantise the rows, un-tile, matmul
-    in f32; only its last-ulp rounding may differ from the kernel's. The CPU
+    in f32; only its last-ulp rounding may differ from the kernels'. The CPU
     runs the reference."""
     K = x.shape[-1]
     M = x.numel() // K
     if not _on_gpu(x):
         return ref.linear_w8(x, ref.unpack_w8(packed), w_scale, residual, bias)
-    if (x.dtype == torch.bfloat16 and 1 <= M <= 32 and K % 128 == 0
-            and N % 64 == 0 and os.environ.get("BBAMD_W8_KERNEL", "1") != "0"):
+    if (x.dtype == torch.bfloat16 and M >= 1 and K % 128 == 0
+            and N % 64 == 0 and os.environ.get("BBAMD_W8_KERNEL", "1") != "0"
+            and (M <= 32 or os.environ.get("BBAMD_W8_TILED", "1") != "0")):
         _require_ext()
         a8, a_scale = hip_w8.quant_rows_fp8(x.contiguous())
         if residual is not None:
             residual = residual.contiguous()
-        return hip_w8.gemm_w8(a8, a_scale, packed, w_scale, residual, bias, N)
+        gemm = hip_w8.gemm_w8 if M <= 32 else hip_w8.gemm_w8_tiled
+        return gemm(a8, a_scale, packed, w_scale, residual, bias, N)
     return ref.linear_w8(x, ref.unpack_w8(packed), w_scale, residual, bias)
 
 

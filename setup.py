@@ -62,7 +62,7 @@ def _run(cmds, verbose: bool) -> None:
 
 def build_w8(verbose: bool = True) -> Path:
     """_hip_w8.so: the fp8 (e4m3) weight tier, bindings (w8_ext.hip) and
-    kernels (gemm_w8.hip) in one translation unit, built without packed-fp32
+    kernels (gemm_w8.hip, gemm_w8_tiled.hip) in one translation unit, built without packed-fp32
     instructions."""
     obj = HIP_DIR / "w8_ext.o"
     compile_cmd = [
