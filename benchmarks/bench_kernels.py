@@ -3,7 +3,7 @@
 Reports per-kernel time and effective HBM bandwidth / TFLOPs so kernel
 changes can be A/B'd without the end-to-end bench's noise.
 
-    python benchmarks/bench_kernels.py [attn_decode attn_mixed attn_prefill attn_prefill_wide train_attn ...]
+    python benchmarks/bench_kernels.py [attn_decode attn_mixed attn_prefill attn_prefill_wide train_attn ring_fold ...]
 """
 import math
 import os
@@ -471,6 +471,64 @@ def bench_train_attn():
               f"bwd (dQ + dK/dV) {t_b*1e3:7.3f} ms {7*pair/t_b/1e12:6.1f} TF/s")
 
 
+def bench_ring_fold():
+    """The ring-attention fold on the busiest rank of a context-parallel
+    prefill, the last one: one diagonal block and world - 1 full blocks,
+    llama-3-8b head geometry, B 1. Against attn_train_fwd on one causal
+    problem of T = world * T_loc: the same arithmetic without state traffic.
+    Each side's FLOP/s counts its own visible (query, key) pairs, two MFMA
+    products each. Three alternating rounds (median and spread)."""
+    B, Hq, Hkv, D = 1, 32, 8, 128
+    scale = 1.0 / math.sqrt(D)
+    for Tl in (1024, 4096):
+        for world in (2, 8):
+            T = world * Tl
+            gen = torch.Generator(device=DEV).manual_seed(T + world)
+            mk = lambda h: torch.randn(B, T, h, D, generator=gen, device=DEV,
+                                       dtype=torch.bfloat16)
+            qt, kt, vt = mk(Hq), mk(Hkv), mk(Hkv)          # (B, T, H, D)
+            q = qt.permute(0, 2, 1, 3)[:, :, T - Tl:]
+            k, v = (t.permute(0, 2, 1, 3).contiguous() for t in (kt, vt))
+            r = world - 1
+
+            def folds():
+                state = None
+                for src in range(r, -1, -1):
+                    sl = slice(src * Tl, (src + 1) * Tl)
+                    state = ops.attn_ring_fold(q, k[:, :, sl], v[:, :, sl], state,
+                                               r * Tl, src * Tl, scale, 0,
+                                               last=src == 0)
+                return state
+
+            train = lambda: ops.hip_ops.attn_train_fwd(qt, kt, vt, scale, 0, None, False)
+            tr, tt = [], []
+            for _ in range(3):
+                tr.append(_event_time(folds, 10, 3))
+                tt.append(_event_time(train, 10, 3))
+            tr.sort()
+            tt.sort()
+            st = ops.attn_ring_fold(q, k[:, :, r * Tl:], v[:, :, r * Tl:], None,
+                                    r * Tl, r * Tl, scale)
+            t_diag = _event_time(lambda: ops.attn_ring_fold(
+                q, k[:, :, r * Tl:], v[:, :, r * Tl:], None, r * Tl, r * Tl, scale), 10, 3)
+            t_full = _event_time(lambda: ops.attn_ring_fold(
+                q, k[:, :, :Tl], v[:, :, :Tl], st, r * Tl, 0, scale), 10, 3)
+            per_pair = B * Hq * D * 2.0 * 2.0
+            f_ring = per_pair * (Tl * (Tl + 1) / 2 + r * Tl * Tl)
+            f_train = per_pair * (T * (T + 1) / 2)
+            state_mb = B * Hq * Tl * (D + 2) * 4 / 2**20
+            print(f"ring_fold T_loc{Tl} world{world} Hq{Hq}/{Hkv} D{D}: "
+                  f"last rank {tr[1]*1e3:8.3f} ms [{tr[0]*1e3:.3f}..{tr[2]*1e3:.3f}] "
+                  f"{f_ring/tr[1]/1e12:6.1f} TF/s | attn_train_fwd T{T} "
+                  f"{tt[1]*1e3:8.3f} ms [{tt[0]*1e3:.3f}..{tt[2]*1e3:.3f}] "
+                  f"{f_train/tt[1]/1e12:6.1f} TF/s | FLOP/s ratio "
+                  f"{(f_ring/tr[1])/(f_train/tt[1]):5.2f}")
+            print(f"    diagonal fold {t_diag*1e3:7.3f} ms "
+                  f"{per_pair*Tl*(Tl+1)/2/t_diag/1e12:6.1f} TF/s   full fold "
+                  f"{t_full*1e3:7.3f} ms {per_pair*Tl*Tl/t_full/1e12:6.1f} TF/s   "
+                  f"state {state_mb:.1f} MiB read + written per fold")
+
+
 def bench_moe_w4():
     """Grouped expert GEMM, 4-bit weights (moe_gemm_w4.hip) beside the bf16
     grouped kernel (moe_gemm.hip) at the Mixtral-8x7B shapes: E = 8, gate_up
@@ -737,6 +795,7 @@ ALL = {
     "swiglu": bench_swiglu,
     "gemm": bench_gemm,
     "gemm_norm": bench_gemm_norm,
+    "ring_fold": bench_ring_fold,
     "moe_w4": bench_moe_w4,
     "w4_tiled": bench_w4_tiled,
     "w8": bench_w8,

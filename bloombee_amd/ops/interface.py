@@ -25,9 +25,11 @@ try:
     hip_ops = importlib.import_module("bloombee_amd.ops._hip_ops")
     # the fp8 weight tier's bindings (ops/hip/w8_ext.hip), a module of its own
     hip_w8 = importlib.import_module("bloombee_amd.ops._hip_w8")
+    # the ring-attention fold's bindings (ops/hip/ring_ext.hip), likewise
+    hip_ring = importlib.import_module("bloombee_amd.ops._hip_ring")
     HAVE_HIP_OPS = True
 except ImportError as e:  # pragma: no cover
-    hip_ops = hip_w8 = None
+    hip_ops = hip_w8 = hip_ring = None
     HAVE_HIP_OPS = False
     _import_error = e
 
@@ -993,3 +995,38 @@ def attn_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
                                              dtype=torch.float32).contiguous()
         return _AttnTrainFn.apply(q, k, v, float(scale), int(window), alibi)
     return ref.attn_train(q, k, v, scale, window, alibi_slopes)
+
+
+# ---------------------------------------------------------------------------
+# ring attention (context parallelism)
+# ---------------------------------------------------------------------------
+
+
+def ring_kernel_ok(q: torch.Tensor) -> bool:
+    """Whether a ring fold of these queries takes the gfx950 kernel: bf16 on
+    the device, head dim 64 or 128, BBAMD_RING_KERNEL (read per call) not 0."""
+    return (_on_gpu(q) and q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128)
+            and os.environ.get("BBAMD_RING_KERNEL", "1") != "0")
+
+
+def attn_ring_fold(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, state,
+                   q_pos0: int, k_pos0: int, scale: float, window: int = 0,
+                   last: bool = False):
+    """One ring-attention step: fold the visiting block k/v (B, Hkv, S, D)
+    into the online-softmax state of q (B, Hq, T, D, any view with a
+    contiguous last dim); see reference.attn_ring_fold for the definition.
+
+    state is None for the first fold, otherwise what the previous call
+    returned; callers only hand it back. last=True returns the normalised
+    output (B, T, Hq, D) instead of a state. bf16 device tensors with
+    D in {64, 128} run the gfx950 kernel (BBAMD_RING_KERNEL=0, read per call,
+    turns it off); everything else takes the torch definition. Both keep the
+    state in the same format."""
+    if ring_kernel_ok(q):
+        _require_ext()
+        q, k, v = (t if _train_view_ok(t) else t.contiguous() for t in (q, k, v))
+        acc, ml = state if state is not None else (None, None)
+        ret = hip_ring.attn_ring_fold(q, k, v, acc, ml, int(k_pos0) - int(q_pos0),
+                                      float(scale), int(window), bool(last))
+        return ret[0] if last else (ret[0], ret[1])
+    return ref.attn_ring_fold(q, k, v, state, q_pos0, k_pos0, scale, window, last)

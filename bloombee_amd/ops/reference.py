@@ -673,3 +673,56 @@ def attn_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
     p = torch.softmax(scores, dim=-1)
     out = torch.matmul(p, v.float()).to(q.dtype)
     return out.permute(0, 2, 1, 3)
+
+
+def attn_ring_fold(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, state,
+                   q_pos0: int, k_pos0: int, scale: float, window: int = 0,
+                   last: bool = False):
+    """One ring-attention step (the definition; ops/hip/attn_ring.hip is its
+    kernel form): fold the visiting block k/v (B, Hkv, S, D) into the
+    online-softmax state of the queries q (B, Hq, T, D).
+
+    Query row t sits at q_pos0 + t, key c at k_pos0 + c; a key is visible iff
+    k_pos0 + c <= q_pos0 + t and, with window > 0, k_pos0 + c >
+    q_pos0 + t - window. state is None (first fold) or (acc, ml) as an earlier
+    call returned it: acc (B, Hq, T, D) f32 unnormalised, ml (B, Hq, T, 2) f32
+    = running max in the exp2 domain (-inf while a row has seen no key) and
+    running sum. A row with no visible key in this block keeps its state.
+    Returns the new state, or with last=True the normalised output
+    (B, T, Hq, D) in q's dtype (zeros for rows that never saw a key).
+    GQA is a view; scores are formed 1024 query rows at a time."""
+    B, Hq, T, D = q.shape
+    Hkv, S = k.shape[1], k.shape[2]
+    G = Hq // Hkv
+    dev = q.device
+    if state is None:
+        acc = torch.zeros(B, Hq, T, D, dtype=torch.float32, device=dev)
+        ml = torch.zeros(B, Hq, T, 2, dtype=torch.float32, device=dev)
+        ml[..., 0] = float("-inf")
+    else:
+        acc, ml = (t.clone(memory_format=torch.contiguous_format) for t in state)
+    kt = k.float().transpose(-1, -2).unsqueeze(2)          # (B, Hkv, 1, D, S)
+    vf = v.float().unsqueeze(2)                            # (B, Hkv, 1, S, D)
+    q5 = q.reshape(B, Hkv, G, T, D)
+    acc5, ml5 = acc.view(B, Hkv, G, T, D), ml.view(B, Hkv, G, T, 2)
+    col = k_pos0 + torch.arange(S, device=dev).view(1, S)
+    for t0 in range(0, T, 1024):
+        t1 = min(T, t0 + 1024)
+        s = torch.matmul(q5[..., t0:t1, :].float(), kt) * (scale * 1.4426950408889634)
+        rowp = q_pos0 + torch.arange(t0, t1, device=dev).view(-1, 1)
+        dead = col > rowp
+        if window > 0:
+            dead = dead | (col <= rowp - window)
+        s = s.masked_fill(dead, float("-inf"))
+        m = ml5[..., t0:t1, 0:1]
+        m_new = torch.maximum(m, s.amax(-1, keepdim=True))
+        m_safe = torch.where(torch.isinf(m_new), torch.zeros_like(m_new), m_new)
+        p = torch.exp2(s - m_safe)
+        corr = torch.exp2(m - m_safe)
+        acc5[..., t0:t1, :] = acc5[..., t0:t1, :] * corr + torch.matmul(p, vf)
+        ml5[..., t0:t1, 1:2] = ml5[..., t0:t1, 1:2] * corr + p.sum(-1, keepdim=True)
+        ml5[..., t0:t1, 0:1] = m_new
+    if not last:
+        return acc, ml
+    out = acc / ml[..., 1:2].clamp_min(1e-30)
+    return out.to(q.dtype).permute(0, 2, 1, 3).contiguous()

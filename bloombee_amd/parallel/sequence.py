@@ -68,73 +68,120 @@ def _ring_exchange(t: torch.Tensor, rank: int, world: int,
     return out
 
 
+def _ring_blocks(k: torch.Tensor, v: torch.Tensor, rank: int, world: int,
+                 group=None):
+    """The ring as this rank sees it: (src, k, v) of the own shard first, then
+    rank-1, rank-2, ... as the blocks arrive. Every exchange is made, also for
+    blocks the consumer does not fold."""
+    src = rank
+    for step in range(world):
+        yield src, k, v
+        if step < world - 1:
+            k = _ring_exchange(k, rank, world, group)
+            v = _ring_exchange(v, rank, world, group)
+            src = (src - 1) % world
+
+
+def _ring_payload(t: torch.Tensor, kernel: bool) -> torch.Tensor:
+    """K/V as they travel: bf16 in the layout the kernel reads, else f32."""
+    return t.contiguous() if kernel else t.float().contiguous()
+
+
+def _ring_fold_all(q: torch.Tensor, blocks, rank: int, world: int,
+                   scale: float, window: int = 0) -> torch.Tensor:
+    """A rank's whole fold sequence over `blocks` (an iterable of
+    (src, k, v), consumed to its end). q (B, Hq, T, D) sits at global rows
+    [rank*T, (rank+1)*T), block src at keys [src*T, (src+1)*T); k/v are
+    (B, Hkv, T, D). Future shards are skipped, and with a window so are
+    blocks wholly below every row's window. Returns (B, Hq, T, D) in q's dtype.
+
+    bf16 device tensors with head dim 64/128 take ops.attn_ring_fold (one
+    launch per visible block, `last` on the final one, GQA inside the kernel);
+    everything else the torch composition over _fold."""
+    from bloombee_amd import ops
+
+    B, Hq, T, D = q.shape
+    dev = q.device
+
+    def visible(src):
+        return src <= rank and (window <= 0
+                                or (src + 1) * T - 1 > rank * T - window)
+
+    final = min(s for s in range(world) if visible(s))
+    if ops.ring_kernel_ok(q):
+        state = out = None
+        for src, kc, vc in blocks:
+            if not visible(src):
+                continue
+            res = ops.attn_ring_fold(q, kc, vc, state, rank * T, src * T, scale,
+                                     window, last=src == final)
+            if src == final:
+                out = res
+            else:
+                state = res
+        return out.permute(0, 2, 1, 3)
+
+    qf = q.float()
+    state = (torch.full((B, Hq, T, 1), float("-inf"), device=dev),
+             torch.zeros(B, Hq, T, 1, device=dev),
+             torch.zeros(B, Hq, T, D, device=dev))
+    row_pos = torch.arange(rank * T, (rank + 1) * T, device=dev)
+    for src, kc, vc in blocks:
+        if not visible(src):
+            continue
+        G = Hq // kc.shape[1]
+        kc, vc = kc.float(), vc.float()
+        if G > 1:
+            kc = kc.repeat_interleave(G, dim=1)
+            vc = vc.repeat_interleave(G, dim=1)
+        s = (qf @ kc.transpose(-1, -2)) * scale
+        if src == rank or window > 0:
+            col_pos = torch.arange(src * T, (src + 1) * T, device=dev)
+            state = _fold(state, s, vc, row_pos, col_pos, window=window)
+        else:
+            state = _fold(state, s, vc)
+    m, l, acc = state
+    return (acc / l.clamp_min(1e-30)).to(q.dtype)
+
+
 def ring_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                    rank: int, world: int, group=None,
                    scale: Optional[float] = None) -> torch.Tensor:
     """Causal attention over a sequence sharded as contiguous T_loc blocks.
 
-    q/k/v: (B, H, T_loc, D) — this rank's shard (global positions
-    [rank*T_loc, (rank+1)*T_loc)). Returns (B, H, T_loc, D)."""
-    B, H, T, D = q.shape
+    q (B, Hq, T_loc, D), k/v (B, Hkv, T_loc, D) — this rank's shard (global
+    positions [rank*T_loc, (rank+1)*T_loc)). Returns (B, Hq, T_loc, D)."""
+    from bloombee_amd import ops
+
     if scale is None:
-        scale = 1.0 / math.sqrt(D)
-    qf = q.float()
-    state = (torch.full((B, H, T, 1), float("-inf")),
-             torch.zeros(B, H, T, 1),
-             torch.zeros(B, H, T, D))
-    row_pos = torch.arange(rank * T, (rank + 1) * T)
-    k_cur, v_cur = k.float(), v.float()
-    src = rank
-    for step in range(world):
-        if src < rank:
-            s = (qf @ k_cur.transpose(-1, -2)) * scale
-            state = _fold(state, s, v_cur)
-        elif src == rank:
-            s = (qf @ k_cur.transpose(-1, -2)) * scale
-            col_pos = torch.arange(src * T, (src + 1) * T)
-            state = _fold(state, s, v_cur, row_pos, col_pos)
-        # else: future shard — causally invisible, just keep rotating
-        if step < world - 1:
-            k_cur = _ring_exchange(k_cur, rank, world, group)
-            v_cur = _ring_exchange(v_cur, rank, world, group)
-            src = (src - 1) % world
-    m, l, acc = state
-    return (acc / l.clamp_min(1e-30)).to(q.dtype)
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    kern = ops.ring_kernel_ok(q)
+    blocks = _ring_blocks(_ring_payload(k, kern), _ring_payload(v, kern),
+                          rank, world, group)
+    return _ring_fold_all(q, blocks, rank, world, scale)
 
 
 def ring_attention_local(q, k, v, world: int,
-                         scale: Optional[float] = None) -> torch.Tensor:
+                         scale: Optional[float] = None,
+                         window: int = 0) -> torch.Tensor:
     """Single-process simulation of the ring over `world` shards (unit-tests
-    the fold/rotation logic at any depth without process groups).
+    the fold/rotation logic at any depth without process groups; the folds are
+    the ones the distributed ring runs).
 
-    q/k/v: (B, H, T_total, D) with world | T_total. Returns full output."""
-    B, H, T, D = q.shape
+    q (B, Hq, T_total, D), k/v (B, Hkv, T_total, D) with world | T_total.
+    Returns the full output (B, Hq, T_total, D)."""
+    T = q.shape[2]
     Tl = T // world
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
     outs = []
     for r in range(world):
-        qr = q[:, :, r * Tl:(r + 1) * Tl].float()
-        if scale is None:
-            sc = 1.0 / math.sqrt(D)
-        else:
-            sc = scale
-        state = (torch.full((B, H, Tl, 1), float("-inf")),
-                 torch.zeros(B, H, Tl, 1),
-                 torch.zeros(B, H, Tl, D))
-        row_pos = torch.arange(r * Tl, (r + 1) * Tl)
         # same visitation order as the ring: own shard first, then r-1, ...
-        for src in [r] + [(r - 1 - i) % world for i in range(world - 1)]:
-            if src > r:
-                continue
-            kc = k[:, :, src * Tl:(src + 1) * Tl].float()
-            vc = v[:, :, src * Tl:(src + 1) * Tl].float()
-            s = (qr @ kc.transpose(-1, -2)) * sc
-            if src == r:
-                col_pos = torch.arange(src * Tl, (src + 1) * Tl)
-                state = _fold(state, s, vc, row_pos, col_pos)
-            else:
-                state = _fold(state, s, vc)
-        m, l, acc = state
-        outs.append((acc / l.clamp_min(1e-30)).to(q.dtype))
+        order = [r] + [(r - 1 - i) % world for i in range(world - 1)]
+        blocks = ((src, k[:, :, src * Tl:(src + 1) * Tl],
+                   v[:, :, src * Tl:(src + 1) * Tl]) for src in order)
+        outs.append(_ring_fold_all(q[:, :, r * Tl:(r + 1) * Tl], blocks, r,
+                                   world, scale, window))
     return torch.cat(outs, dim=2)
 
 
@@ -171,7 +218,6 @@ def cp_prefill_llama(stack, kv_handle, hidden_shard: torch.Tensor,
             raise NotImplementedError(
                 "cp_prefill_llama supports llama-pattern blocks")
         Hq, Hkv, D = blk.Hq, blk.Hkv, blk.D
-        G = Hq // Hkv
         x = rms_train(hidden, blk.input_norm_w, eps)
         qkv = (F.linear(x, blk.qkv_w).view(B, T_loc, Hq + 2 * Hkv, D)
                .permute(0, 2, 1, 3))
@@ -186,32 +232,13 @@ def cp_prefill_llama(stack, kv_handle, hidden_shard: torch.Tensor,
                .view(1, T_loc).expand(B, T_loc))
         q, k = refops.rope_apply(q.contiguous(), k.contiguous(), cos, sin, pos)
 
-        # ring attention with Hkv-width exchange, GQA expansion per fold
-        qf = q.float()
-        state = (torch.full((B, Hq, T_loc, 1), float("-inf")),
-                 torch.zeros(B, Hq, T_loc, 1),
-                 torch.zeros(B, Hq, T_loc, D))
-        row_pos = torch.arange(rank * T_loc, (rank + 1) * T_loc)
-        k_cur = k.float().contiguous()
-        v_cur = v.float().contiguous()
-        src = rank
-        for step in range(world):
-            if src <= rank:
-                kx = k_cur.repeat_interleave(G, dim=1)
-                vx = v_cur.repeat_interleave(G, dim=1)
-                s = (qf @ kx.transpose(-1, -2)) * blk.scale
-                if src == rank:
-                    col_pos = torch.arange(src * T_loc, (src + 1) * T_loc)
-                    state = _fold(state, s, vx, row_pos, col_pos)
-                else:
-                    state = _fold(state, s, vx)
-            if step < world - 1:
-                k_cur = _ring_exchange(k_cur, rank, world, group)
-                v_cur = _ring_exchange(v_cur, rank, world, group)
-                src = (src - 1) % world
-        m, l, acc = state
-        attn = ((acc / l.clamp_min(1e-30)).to(hidden.dtype)
-                .permute(0, 2, 1, 3).reshape(B, T_loc, Hq * D))
+        # ring attention with Hkv-width exchange; GQA inside the fold
+        kern = ops.ring_kernel_ok(q)
+        blocks = _ring_blocks(_ring_payload(k, kern), _ring_payload(v, kern),
+                              rank, world, group)
+        attn = (_ring_fold_all(q, blocks, rank, world, blk.scale)
+                .to(hidden.dtype).permute(0, 2, 1, 3)
+                .reshape(B, T_loc, Hq * D))
 
         h2 = hidden + F.linear(attn, blk.o_w)
         y = rms_train(h2, blk.post_norm_w, eps)
@@ -298,10 +325,10 @@ def cp_prefill_gemma4(stack, kv_handle, hidden_shard: torch.Tensor,
             k, v = donor_kv[blk.donor]           # shared-KV tail
             write_layer = None
 
-        state = (torch.full((B, Hq, T_loc, 1), float("-inf")),
-                 torch.zeros(B, Hq, T_loc, 1),
-                 torch.zeros(B, Hq, T_loc, D))
-        row_pos = torch.arange(rank * T_loc, (rank + 1) * T_loc)
+        state = (torch.full((B, Hq, T_loc, 1), float("-inf"), device=dev),
+                 torch.zeros(B, Hq, T_loc, 1, device=dev),
+                 torch.zeros(B, Hq, T_loc, D, device=dev))
+        row_pos = torch.arange(rank * T_loc, (rank + 1) * T_loc, device=dev)
         win = blk.window
         k_cur = k.float().contiguous()
         v_cur = v.float().contiguous()
@@ -312,7 +339,8 @@ def cp_prefill_gemma4(stack, kv_handle, hidden_shard: torch.Tensor,
                 kx = k_cur.repeat_interleave(G, dim=1)
                 vx = v_cur.repeat_interleave(G, dim=1)
                 s = qf @ kx.transpose(-1, -2)    # gemma scale = 1.0
-                col_pos = torch.arange(src * T_loc, (src + 1) * T_loc)
+                col_pos = torch.arange(src * T_loc, (src + 1) * T_loc,
+                                       device=dev)
                 if src == rank or win > 0:
                     state = _fold(state, s, vx, row_pos, col_pos, window=win)
                 else:

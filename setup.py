@@ -18,6 +18,7 @@ ROOT = Path(__file__).resolve().parent
 HIP_DIR = ROOT / "bloombee_amd" / "ops" / "hip"
 OUT_SO = ROOT / "bloombee_amd" / "ops" / "_hip_ops.so"
 W8_SO = ROOT / "bloombee_amd" / "ops" / "_hip_w8.so"
+RING_SO = ROOT / "bloombee_amd" / "ops" / "_hip_ring.so"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 
@@ -77,6 +78,21 @@ def build_w8(verbose: bool = True) -> Path:
     return W8_SO
 
 
+def build_ring(verbose: bool = True) -> Path:
+    """_hip_ring.so: the ring-attention fold, bindings (ring_ext.hip) and
+    kernel (attn_ring.hip) in one translation unit."""
+    obj = HIP_DIR / "ring_ext.o"
+    compile_cmd = [
+        "/opt/rocm/bin/hipcc", f"--offload-arch={ARCH}",
+        "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
+        *_torch_ext_flags("_hip_ring"),
+        "-c", str(HIP_DIR / "ring_ext.hip"), "-o", str(obj),
+    ]
+    _run((compile_cmd, _link([obj], RING_SO)), verbose)
+    obj.unlink(missing_ok=True)
+    return RING_SO
+
+
 def build(verbose: bool = True) -> Path:
     src = HIP_DIR / "ext.hip"
     obj = HIP_DIR / "ext.o"
@@ -101,6 +117,7 @@ def build(verbose: bool = True) -> Path:
     obj.unlink(missing_ok=True)
     kv8_obj.unlink(missing_ok=True)
     build_w8(verbose)
+    build_ring(verbose)
     return OUT_SO
 
 
